@@ -19,12 +19,20 @@ with dropout + SpecAugment -> BCE/MSE losses) + EMA + backward + [gradient all-r
 on one batch of 48 synthetic 10 s / 16 kHz clips per GPU (12 strong / 12 weak / 24 unlabelled), already resident in
 HBM.  Weak scaling: every rank runs the reference's single-GPU step on its own clips; gradients are averaged.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the kernel that dominates the step -- the launch shape with the largest
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the line: `metric`, `value` (clips/s),
+`ms_per_step` and the configuration.  `--dump-outputs DIR` also writes what the last timed step handed its caller -- the loss, the
+logged metrics, the student's and the teacher's state after the step -- as DIR/<name>.npy (float32 / float64); the inputs are
+seeded, so two builds of the library can be compared output for output.
+
+`--full` adds every other measurement, each after the timed region:
+`roofline` is for the kernel that dominates the step -- the launch shape with the largest
 total time per step over ALL C-ABI entry points, every launch bracketed by HIP events on its stream over 5 eager steps right
 after the timed region -- as algorithmic work per launch / mean launch time against the roof that bounds it;
 `roofline_families` is the same accounting per kernel family (mel, block0, conv, glu, wgrad, gru, gemm, head+loss, optim).
 `cpu_baseline` times the CPU oracle (oracle/sed_oracle.py, the unfused torch restatement of the reference step) on this
-host's cores at the same batch of 48 clips, rank 0, N=1 only.
+host's cores at the same batch of 48 clips, rank 0, N=1 only (not with --no-cpu-baseline).  The default surface also times K
+steps of the driver called by hand (`config.surface.driver_surface_ms_per_step`), and N > 1 runs probe the exchange tail
+(`dist.exchange_tail_us`).
 """
 import argparse
 import json
@@ -350,6 +358,24 @@ def cpu_baseline_bounded():
     return {"value": round(best["clips_per_s"], 3), "unit": "clips/s", "cores": best["threads"], "kind": "port", "sample": head + desc}
 
 
+def step_outputs(task, loss):
+    """What a training step hands its caller, copied to the host: the returned loss, every logged metric, and the student's and the
+    teacher's state after the step (the floating-point entries of state_dict(), in key order, flattened and concatenated: ~9 MB)."""
+    out = {"loss": np.asarray(float(loss), dtype=np.float64)}
+    for name, value in task.logged.items():
+        out["log_" + name.replace("/", "_")] = np.asarray(float(value), dtype=np.float64)
+    for tag, model in (("student", task.sed_student), ("teacher", task.sed_teacher)):
+        flat = [t.detach().reshape(-1).float() for t in model.state_dict().values() if t.is_floating_point()]
+        out[tag + "_state"] = torch.cat(flat).cpu().numpy()
+    return out
+
+
+def write_outputs(outputs, path):
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def rccl_debug_lines(limit=12):
     """With NCCL_DEBUG=INFO: what RCCL itself says it runs -- the lines of this rank's debug file that name an algorithm / protocol
     / ring or tree (main() points NCCL_DEBUG_FILE at /tmp/sed_bench_rccl_<pid>.log).  None when RCCL debugging is off."""
@@ -416,6 +442,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)        # >= 50 timed steps after >= 10 warm-up
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure everything beyond the headline: per-launch rooflines (5 eager steps), "
+                         "the CPU baseline, the driver-surface comparison, the exchange-tail probe at N > 1")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (loss, logged metrics, student and teacher state) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of replaying the captured hipGraph step")
     ap.add_argument("--surface", choices=("lightning", "driver"), default="lightning",
@@ -462,7 +493,8 @@ def main():
     ap.add_argument("--ts-probe", action="store_true",
                     help="diagnostics: GPU wall-clock stamps inside the replayed step (tools/ts_probe.py); adds ~10 one-thread kernels")
     ap.add_argument("--dump-launches", default=None, metavar="PATH",
-                    help="diagnostics: write every launch shape's median time (the rows behind roofline_families) as JSON to PATH")
+                    help="diagnostics: write every launch shape's median time (the rows behind roofline_families) as JSON to PATH; "
+                         "runs the per-launch timing of --full")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: run the same program on the CPU emulator of the kernels over gloo at toy sizes (launch-path check "
                          "only, the numbers are meaningless)")
@@ -623,9 +655,8 @@ def main():
         else:
             batch, nxt = (inputs["audio"], labels if captured else labels.clone(), None, inputs["emb"]), (inputs["next_audio"], next_labels(), None, None)
         if pipelined:       # the loader hands over batch k and announces batch k + 1 (synthetic: the same clips again)
-            driver.run_step(batch, i, next_batch=nxt)
-        else:
-            driver.run_step(batch, i)
+            return driver.run_step(batch, i, next_batch=nxt)
+        return driver.run_step(batch, i)
 
     def sync():
         if not dry:
@@ -647,9 +678,11 @@ def main():
             if inputs["next_labels"] is not None:
                 inputs["next_labels"].copy_(labels)
 
+    measure_launches = args.full or args.dump_launches is not None     # the per-launch timing after the timed region
     # untimed: the W warm-up steps, plus (graph mode) whatever is still missing for the capture to lie outside the timed region
     n_untimed = max(args.warmup, 5) if use_graph else args.warmup
     graph_note = None
+    outputs = None                  # --dump-outputs: the last timed step's results, on the host
     surface_info = None
     out_metric_note = ""
     if lightning:
@@ -677,7 +710,7 @@ def main():
         marks = {}
 
         def on_step(tr, model, i):
-            nonlocal driver
+            nonlocal driver, outputs
             n = i + 1
             driver = task._driver
             if n == n_untimed - 3 and host is None:
@@ -695,6 +728,8 @@ def main():
                 marks["t1"] = time.perf_counter()
                 if driver is not None and getattr(driver, "graph", None) is not None:
                     marks["fallbacks"], marks["reprimes"] = driver.eager_fallbacks, driver.reprimes
+                if args.dump_outputs:           # (before the epoch's last batch runs: the graph rewrites its static outputs)
+                    outputs = step_outputs(task, tr.losses[-1])
 
         Trainer(max_epochs=1, on_step=on_step).fit(task)
         sync()
@@ -713,10 +748,11 @@ def main():
         if host is not None:
             out_metric_note = "PCIe-INCLUSIVE (pinned host batches, one host-to-device copy of the next batch per step) "
         if driver is None:
-            # hooks mode (--no-graph): the per-launch timing below still needs a StepDriver for its eager steps
-            driver = StepDriver(task, world_size=1, prefetch="off")
-            pipelined = False
-        else:
+            if measure_launches:
+                # hooks mode (--no-graph): the per-launch timing below still needs a StepDriver for its eager steps
+                driver = StepDriver(task, world_size=1, prefetch="off")
+                pipelined = False
+        elif args.full:
             # the same captured step driven by hand (StepDriver protocol, what --surface driver times): K more steps, after the epoch's
             # last batch has been run eagerly -- 3 untimed steps re-prime the pipeline
             for i in range(3):
@@ -752,7 +788,7 @@ def main():
         sync()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            one_step(args.warmup + i)
+            loss = one_step(args.warmup + i)
         sync()
         dt_local = time.perf_counter() - t0             # this rank's own K steps (before it waits for the others)
     ts_rows = None
@@ -765,10 +801,12 @@ def main():
             dist.barrier()
         sync()
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            outputs = step_outputs(task, loss)
     # Data-parallel runs: PROBE_STEPS more steps of the SAME launch path (graph replays + eager exchange tail, or eager steps) with
     # marks around the exchange tail -- after the timed region, so the K timed steps carry no extra events.
     exchange_probe = None
-    if grouped:
+    if grouped and args.full:
         from desed_task_amd.launcher import ExchangeProbe
         PROBE_STEPS = 2 if dry else 7
         d0 = driver.eager if use_graph else driver
@@ -784,8 +822,9 @@ def main():
     # them is not recorded -- it re-warms the eager path after the graph replays -- and every entry reports its MEDIAN launch).
     EAGER_STEPS = 5
     timer = KernelTimer(None)
-    eager = driver.eager if use_graph else driver
-    if not dry:
+    if measure_launches and not dry:
+        eager = driver.eager if use_graph else driver
+
         def eager_step(i):
             batch = (inputs["audio"], labels.clone(), None, emb)
             if pipelined:
@@ -942,8 +981,13 @@ def main():
     if dry:
         out["dry_run"] = True
         out["data"] = "synthetic, toy sizes (%d clips of %d samples per rank) on the CPU emulator" % (sum(BATCH), N_SAMPLES)
-    if world == 1 and not args.no_cpu_baseline and not args.embeddings and not dry:
+    if not timer.records:               # the per-launch timing did not run (a plain run, or the CPU emulator)
+        for k in ("roofline", "roofline_families", "roofline_top_launches"):
+            del out[k]
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.embeddings and not dry:
         out["cpu_baseline"] = cpu_baseline_bounded()
+    if outputs is not None:
+        write_outputs(outputs, args.dump_outputs)
     sys.stdout.flush()
     try:
         import ctypes
