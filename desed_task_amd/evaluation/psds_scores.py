@@ -27,10 +27,11 @@ from .psds import PSDSEval
 
 def read_ground_truth_events(path):
     """{audio_id: [(onset, offset, event_label), ...]} from a filename / onset / offset / event_label TSV; clips whose only row
-    has no event map to [] (sed_scores_eval.io.read_ground_truth_events, used at sed_trainer.py:503,736)."""
+    has no event map to [] (sed_scores_eval.io.read_ground_truth_events, used at sed_trainer.py:503,736).  `path` may also be the
+    table itself, as the 2024 recipe passes it (sed_trainer_pretrained.py:682, :1157)."""
     if isinstance(path, dict):
         return path
-    df = pd.read_csv(path, sep="\t")
+    df = path if isinstance(path, pd.DataFrame) else pd.read_csv(path, sep="\t")
     out = {}
     for rec in df.to_dict("records"):
         events = out.setdefault(Path(str(rec["filename"])).stem, [])

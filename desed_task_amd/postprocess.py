@@ -8,7 +8,13 @@ arrays with ONE synchronising copy; only the frame -> seconds conversion and the
 
 `batched_decode_preds` keeps the reference's signature and return value (scores_raw, scores_postprocessed,
 prediction_dfs).  `create_score_dataframe` (sed_scores_eval, third party, absent from the reference tree) is restated
-below from its documented output format: columns onset, offset, then one column per event class."""
+below from its documented output format: columns onset, offset, then one column per event class.
+
+The 2024 recipe (recipes/dcase2024_task4_baseline/local/utils.py:30-99) passes `median_filter` as a callable instead: None (no
+filtering) or desed_task.utils.postprocess.ClassWiseMedianFilter (one window length per class).  `ClassWiseMedianFilter` below
+is that class; handed to `batched_decode_preds` it runs as ONE device launch per batch (`median_filter_classwise`).
+`segment_scores` turns frame scores into segment scores on the device (the 2024 test path's MAESTRO scoring)."""
+import numbers
 from pathlib import Path
 
 import numpy as np
@@ -31,6 +37,68 @@ def median_filter_scores(scores_btc, win=7):
     B, T, NC = scores_btc.shape
     out = torch.empty_like(scores_btc)
     _lib.get().call("sed_median_filter", scores_btc.data_ptr(), out.data_ptr(), B, T, NC, int(win), _lib.stream_ptr(scores_btc))
+    return out
+
+
+class ClassWiseMedianFilter:
+    """desed_task/utils/postprocess.py:5-18: `filter_lens[c]` is the median window (frames) of class c.  Called on a (T, NC)
+    numpy array it is the reference's host filter -- scipy.ndimage.median_filter(x[:, c:c+1], (filter_lens[c], 1)) per class.
+    `batched_decode_preds(median_filter=<this>)` runs the same filter for the whole batch on the device instead."""
+
+    def __init__(self, filter_lens=(1, 1, 1)):
+        self.filter_lens = filter_lens
+        self._dev = {}
+
+    def __call__(self, x, **kwargs):
+        from scipy.ndimage import median_filter
+        out = []
+        for c in range(x.shape[-1]):
+            out.append(median_filter(x[..., c][..., None], (self.filter_lens[c], 1))[:, 0])
+        return np.stack(out, -1)
+
+    def device_windows(self, device):
+        """The window lengths as an int32 tensor on `device` (made once per device)."""
+        key = (str(device), tuple(int(w) for w in self.filter_lens))
+        if key not in self._dev:
+            self._dev = {key: torch.tensor(key[1], dtype=torch.int32, device=device)}
+        return self._dev[key]
+
+
+def median_filter_classwise(scores_btc, wins):
+    """ClassWiseMedianFilter(wins) applied to every clip of scores (B, T, NC) in one launch: bit-exact with scipy.  wins: NC
+    window lengths (sequence, or a ClassWiseMedianFilter), each 1 .. 64; a longer one is refused by the kernel
+    (SED_ERR_UNSUPPORTED) -- there is no host path."""
+    _lib.check_tensor(scores_btc, "scores")
+    B, T, NC = scores_btc.shape
+    filt = wins if isinstance(wins, ClassWiseMedianFilter) else ClassWiseMedianFilter(list(wins))
+    lens = [int(w) for w in filt.filter_lens]
+    if len(lens) != NC:
+        raise ValueError("ClassWiseMedianFilter has %d window lengths for %d classes" % (len(lens), NC))
+    if min(lens) < 1:
+        raise ValueError("median window lengths must be >= 1")
+    out = torch.empty_like(scores_btc)
+    w_dev = filt.device_windows(scores_btc.device)
+    _lib.get().call("sed_median_filter_classwise", scores_btc.data_ptr(), out.data_ptr(), w_dev.data_ptr(), B, T, NC, max(lens),
+                    _lib.stream_ptr(scores_btc))
+    return out
+
+
+def segment_scores(scores_btc, clip_len, frame_hop, segment_length=1.0, n_seg=None, mode=0):
+    """(B, T, NC) frame scores -> (B, n_seg, NC) segment scores on the device.  Frame i = [i * frame_hop, (i + 1) * frame_hop);
+    clip b has ceil(clip_len[b] / segment_length) segments (the rest of its rows are 0).  mode 0: the overlap-weighted mean of
+    the 2024 recipe's _get_segment_scores (sed_trainer_pretrained.py:1457-1490); mode 1: the maximum over overlapping frames."""
+    import math
+    _lib.check_tensor(scores_btc, "scores")
+    B, T, NC = scores_btc.shape
+    lens = torch.as_tensor(clip_len, dtype=torch.float32).reshape(-1)
+    if lens.numel() != B:
+        raise ValueError("one clip length per clip")
+    if n_seg is None:
+        n_seg = max([math.ceil(float(v) / segment_length) for v in lens.tolist()] + [1])
+    lens = lens.to(scores_btc.device)
+    out = torch.empty(B, int(n_seg), NC, dtype=torch.float32, device=scores_btc.device)
+    _lib.get().call("sed_segment_scores", scores_btc.data_ptr(), lens.data_ptr(), out.data_ptr(), B, T, NC, float(frame_hop),
+                    float(segment_length), int(n_seg), int(mode), _lib.stream_ptr(scores_btc))
     return out
 
 
@@ -64,14 +132,32 @@ def create_score_dataframe(scores, timestamps, event_classes):
                         columns=["onset", "offset"] + list(event_classes))
 
 
+def _filter_batch(scores, median_filter):
+    """The post-processing filter of `batched_decode_preds` on (B, T, NC) device scores: int = one window for all classes
+    (2023), None = none (2024 default), ClassWiseMedianFilter = one window per class (2024) -- both on the device; any other
+    callable runs per clip on the host, as in the reference (utils.py:77 of the 2024 recipe)."""
+    if median_filter is None:
+        return scores
+    if isinstance(median_filter, numbers.Number):
+        return median_filter_scores(scores, median_filter)
+    if isinstance(median_filter, ClassWiseMedianFilter):
+        return median_filter_classwise(scores, median_filter)
+    if not callable(median_filter):
+        raise TypeError("median_filter must be an int window, None, or a callable on (frames, classes) arrays")
+    x = scores.cpu().numpy()
+    filt = np.stack([median_filter(x[j]) for j in range(x.shape[0])]).astype(np.float32)
+    return torch.from_numpy(filt).to(scores.device)
+
+
 def batched_decode_preds(strong_preds, filenames, encoder, thresholds=[0.5], median_filter=7, pad_indx=None):  # noqa: B006
-    """Reference signature and return value (utils.py:16-73); `median_filter` is the window length as there.
+    """Reference signature and return value (utils.py:16-73); `median_filter` is the window length as there, or (2024 recipe)
+    None / a ClassWiseMedianFilter / any callable on a clip's (frames, classes) array.  `thresholds=[]` (the 2024 validation)
+    returns the score tables and an empty dict of decodings.
 
     Knowing deviation: with `pad_indx` the reference crops `c_scores[:true_len]` BEFORE transposing, i.e. along the class axis
     of the (NC, T) tensor (utils.py:48-52) -- an inert slip, since no caller of the 2023 recipe passes `pad_indx`.  Here
     `pad_indx` crops the time axis, which is what the argument documents."""
     import pandas as pd
-    win = median_filter
     scores = _btc(strong_preds)                                   # (B, T, NC)
     B, T, NC = scores.shape
     true_len = None
@@ -83,10 +169,13 @@ def batched_decode_preds(strong_preds, filenames, encoder, thresholds=[0.5], med
         for n in sorted(set(true_len)):
             rows = [j for j in range(B) if true_len[j] == n]
             if n > 0:
-                filt[rows, :n] = median_filter_scores(scores[rows, :n].contiguous(), win)
+                filt[rows, :n] = _filter_batch(scores[rows, :n].contiguous(), median_filter)
     else:
-        filt = median_filter_scores(scores, win)
-    counts, events = threshold_events(filt, thresholds, true_len)
+        filt = _filter_batch(scores, median_filter)
+    if len(thresholds) == 0:
+        counts, events = np.zeros((0, B, NC), dtype=np.int32), np.zeros((0, B, NC, 1, 2), dtype=np.int32)
+    else:
+        counts, events = threshold_events(filt, thresholds, true_len)
     raw_np, filt_np = scores.cpu().numpy(), filt.cpu().numpy()
     scores_raw, scores_post = {}, {}
     audio_ids = [Path(f).stem for f in filenames]

@@ -327,6 +327,25 @@ int sed_median_filter(const float* scores, float* out, int B, int T, int NC, int
 int sed_threshold_events(const float* scores, const float* thresholds, const int* true_len, int* counts, int* events,
                          int B, int T, int NC, int n_thr, int max_events, void* stream);
 
+/* ---- 2024 recipe: validation / test post-processing ------------------------------------------------------------------------ */
+
+/* ClassWiseMedianFilter (desed_task/utils/postprocess.py:5-18; recipes/dcase2024_task4_baseline/local/utils.py:77 via
+ * sed_trainer_pretrained.py:545,561,872,896): scipy.ndimage.median_filter(x[:, c:c+1], (wins[c], 1)) for every class c of every
+ * clip -- 'reflect' boundary (repeated when T < wins[c]), origin 0, element wins[c]/2 of the sorted window.  scores / out (B,T,NC)
+ * frame-major; wins (NC) int32 on the device; w_max = the largest entry of wins (the caller holds the list): 1 <= w_max <= 64,
+ * else SED_ERR_UNSUPPORTED.  Contract: every entry lies in [1, w_max].  The kernel cannot report a device-side entry outside
+ * it; it clamps such an entry into [1, w_max] (which keeps every read inside the staged rows) and filters that class with the
+ * clamped length -- a different median, not an error.  Bit-exact (selection). */
+int sed_median_filter_classwise(const float* scores, float* out, const int* wins, int B, int T, int NC, int w_max, void* stream);
+
+/* Segment scores of the 2024 test path (recipes/dcase2024_task4_baseline/local/sed_trainer_pretrained.py:1457-1490): scores
+ * (B,T,NC) with frame i = [i*frame_hop, (i+1)*frame_hop), clip_len (B) float seconds on the device -> out (B,n_seg,NC); segment k
+ * = [k*seg_len, min((k+1)*seg_len, clip_len[b])) exists for k < ceil(clip_len[b] / seg_len) (others are written 0).
+ * mode 0: overlap-weighted mean of _get_segment_scores; mode 1: maximum over the frames overlapping the segment with positive
+ * length (the segment-based evaluator's reduction). */
+int sed_segment_scores(const float* scores, const float* clip_len, float* out, int B, int T, int NC, double frame_hop,
+                       double seg_len, int n_seg, int mode, void* stream);
+
 /* ---- K14: embedding fusion before the recurrent stage, desed_task/nnet/CRNN.py:283-296 -------- */
 
 /* z (B,T,C+E) = dropout(cat(x (B,T,C), adaptive_avg_pool1d(emb (B,E,Te), T)^T)) -- the input of `cat_tf`
