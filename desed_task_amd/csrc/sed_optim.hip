@@ -18,11 +18,13 @@ __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ teacher, c
     }
     if (i == 0) for (size_t j = n4 * 4; j < n; ++j) teacher[j] = teacher[j] * alpha + one_minus_alpha * student[j];
 }
-// teacher <- alpha * teacher + (1 - alpha) * student over n floats (16-byte aligned buffers)
+// teacher <- alpha * teacher + (1 - alpha) * student over n floats.  n >= 4 takes float4 accesses: both buffers 16-byte aligned, else
+// SED_ERR_ARG; n < 4 runs the scalar tail alone and is legal at any alignment (arena.ema_update_'s unaligned 1-3-element tensors).
 SED_API int sed_ema_update(float* teacher, const float* student, long long n, float alpha, float one_minus_alpha,
                               const float* alpha_dev, void* stream) {
     if (n <= 0) return SED_OK;
     const size_t n4 = (size_t)n / 4;
+    if (n4 > 0 && (((uintptr_t)teacher | (uintptr_t)student) & 15) != 0) return SED_ERR_ARG;
     const int grid = (int)((n4 + 255) / 256) + (n4 == 0 ? 1 : 0);
     SED_LAUNCH(ema_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, teacher, student, n4, (size_t)n, alpha, one_minus_alpha,
                alpha_dev);
@@ -56,9 +58,16 @@ SED_API int sed_adam_step(float* p, const float* g, float* m, float* v, long lon
     return sed_check_launch();
 }
 
-// Zero up to four (small) accumulator buffers in one launch; null / 0 entries are skipped.
+// Zero up to four (small) accumulator buffers in one launch; null / 0 entries are skipped.  The kernel indexes with int: a count
+// that does not fit is SED_ERR_UNSUPPORTED (cast to int it would turn negative and the buffer would silently stay as it was).
 SED_API int sed_zero_buffers(float* p0, long long n0, float* p1, long long n1, float* p2, long long n2, float* p3, long long n3,
                                 void* stream) {
+    const long long nmax = 0x7fffffffLL - 255;          // (n + 255) / 256 in sed_zero4 must not overflow either
+    if (n0 > nmax || n1 > nmax || n2 > nmax || n3 > nmax) return SED_ERR_UNSUPPORTED;
+    if (!p0) n0 = 0;
+    if (!p1) n1 = 0;
+    if (!p2) n2 = 0;
+    if (!p3) n3 = 0;
     sed_zero4((hipStream_t)stream, p0, (int)n0, p1, (int)n1, p2, (int)n2, p3, (int)n3);
     return sed_check_launch();
 }

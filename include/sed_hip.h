@@ -367,7 +367,8 @@ int sed_dropstep(const float* x, float* y, const int* bounds, int B, int T, int 
 
 /* ---- K10 + K11: flat parameter arena ------------------------------------------------------------------------- */
 
-/* SEDTask4.update_ema (sed_trainer.py:187-199) over the whole arena: teacher = alpha*teacher + (1-alpha)*student. */
+/* SEDTask4.update_ema (sed_trainer.py:187-199) over the whole arena: teacher = alpha*teacher + (1-alpha)*student.
+ * n >= 4: both buffers 16-byte aligned (float4 accesses), else SED_ERR_ARG; n < 4 is legal at any alignment. */
 int sed_ema_update(float* teacher, const float* student, long long n, float alpha, float one_minus_alpha,
                    const float* alpha_dev, void* stream);
 
@@ -375,7 +376,8 @@ int sed_ema_update(float* teacher, const float* student, long long n, float alph
 int sed_adam_step(float* p, const float* g, float* m, float* v, long long n, float b1, float b2, float eps,
                   float step_size, float inv_bc2_sqrt, float grad_scale, const float* hyper_dev, void* stream);
 
-/* Zero up to four small accumulator buffers in one launch (null / 0 entries are skipped). */
+/* Zero up to four small accumulator buffers in one launch (null / 0 entries are skipped).  Counts are indexed as int:
+ * a count above 2^31 - 256 is SED_ERR_UNSUPPORTED and nothing is zeroed. */
 int sed_zero_buffers(float* p0, long long n0, float* p1, long long n1, float* p2, long long n2, float* p3, long long n3,
                      void* stream);
 
