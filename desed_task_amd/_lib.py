@@ -39,6 +39,11 @@ def parse_header(path=_HEADER):
     return protos
 
 
+def header_constants(path=_HEADER):
+    """-> {name: int} for every `#define SED_NAME <integer>` of the header (sizes the host and the kernels must agree on)."""
+    return {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+(SED_\w+)\s+(\d+)\b", open(path).read(), re.M)}
+
+
 class _Lib:
     def __init__(self, path, is_emulator=False):
         self.path = path

@@ -28,6 +28,22 @@ class LightningModule(torch.nn.Module):
     def backward(self, loss, optimizer=None, optimizer_idx=None, *args, **kwargs):
         loss.backward(*args, **kwargs)
 
+    def configure_gradient_clipping(self, optimizer, optimizer_idx=0, gradient_clip_val=None, gradient_clip_algorithm=None):
+        self.clip_gradients(optimizer, gradient_clip_val=gradient_clip_val, gradient_clip_algorithm=gradient_clip_algorithm)
+
+    def clip_gradients(self, optimizer, gradient_clip_val=None, gradient_clip_algorithm=None):
+        """Lightning's precision plugin: clip_grad_norm_ / clip_grad_value_ over the optimizer's parameters; 0 / None: nothing."""
+        if not gradient_clip_val or gradient_clip_val <= 0:
+            return
+        params = [p for g in optimizer.param_groups for p in g["params"]]
+        algorithm = gradient_clip_algorithm or "norm"
+        if algorithm == "norm":
+            torch.nn.utils.clip_grad_norm_(params, float(gradient_clip_val))
+        elif algorithm == "value":
+            torch.nn.utils.clip_grad_value_(params, clip_value=float(gradient_clip_val))
+        else:
+            raise ValueError("gradient_clip_algorithm %r: 'norm' or 'value'" % (gradient_clip_algorithm,))
+
     def transfer_batch_to_device(self, batch, device, dataloader_idx=0):
         return move_to_device(batch, device)
 

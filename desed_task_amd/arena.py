@@ -107,18 +107,73 @@ class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam(lr, betas, eps) semantics (no weight decay / amsgrad) on the HIP kernel.
     With an arena whose gradients are flat the step is ONE launch; otherwise one launch per tensor.
 
+    `max_grad_norm` (None / 0: off): torch.nn.utils.clip_grad_norm_(params, max_grad_norm, norm_type=2) as Lightning applies the
+    recipes' `gradient_clip` (after backward and the data-parallel average, before the update), on the device and without a host
+    read-back: coef = min(1, max_grad_norm / (|| grad_scale g ||_2 + 1e-6)) and Adam consumes g * grad_scale * coef.  Flat
+    gradients: two launches (sed_grad_sqnorm over the gradient arena, sed_adam_step_clipped); gradients outside an intact arena:
+    gathered into it, one norm launch, then the per-tensor launches all reading the same partial sums; no arena: torch's own
+    clip_grad_norm_ arithmetic on the parameter list, then the per-tensor launches (correct, slow, on no recipe path).  With an
+    arena `p.grad` / `flat_grad` are NOT rewritten -- the deviation from torch that `grad_scale` already makes: after a step
+    `p.grad` holds what backward (and the exchange) wrote, not the clipped value.  `last_clip` = {norm, coef} of the last
+    clipped step, a 2-element device tensor (a view of the one persistent buffer the launches use: a captured hipGraph holds
+    its address, so it is allocated once per device and never replaced by load_state_dict).
+
     State: the moments live in two flat buffers shaped like the arena; `self.state[p]` holds, per parameter, views into
     them under torch.optim.Adam's own keys (`step`, `exp_avg`, `exp_avg_sq`), so `state_dict()` / `load_state_dict()` carry the
     full optimizer state in Adam's layout (what Lightning writes into a checkpoint's `optimizer_states` and reads back on
     resume, train_sed.py:293) and the per-tensor path continues from the same moments.  `arena` may be the ParamArena or
     the model that owns it (`model.arena` is then looked up at every step, so a `.to()` that rebuilt the arena is followed)."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, arena=None, grad_scale=1.0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, arena=None, grad_scale=1.0, max_grad_norm=None):
         defaults = dict(lr=lr, betas=betas, eps=eps)
         super().__init__(params, defaults)
         self._arena_src = arena
         self.grad_scale = grad_scale
         self._flat_state = None
+        self.max_grad_norm = max_grad_norm
+
+    # ---- gradient-norm clipping -----------------------------------------------------------------------------------------------
+    max_grad_norm = None    # (class defaults: adopt() and unpickling make instances without __init__)
+    _clip_once = None       # SEDTask4.configure_gradient_clipping: clip the NEXT update only (Lightning's hook-by-hook order)
+    _clip_buf = None        # {partials (SED_SQNORM_MAX_PARTIALS) | norm, coef | pad}: one device buffer for the optimizer's lifetime
+
+    def arm_clip(self, max_norm):
+        """Clip the next update (one step() call) at `max_norm`, whatever `max_grad_norm` says."""
+        self._clip_once = float(max_norm)
+
+    def _clip_buffer(self, device):
+        buf = self._clip_buf
+        if buf is None or buf.device != device:
+            buf = self._clip_buf = torch.zeros(_lib.header_constants()["SED_SQNORM_MAX_PARTIALS"] + 4, device=device, dtype=torch.float32)
+        return buf
+
+    @property
+    def last_clip(self):
+        """{|| grad_scale g ||_2, coef} of the last clipped update as a 2-element device tensor (None before the first one)."""
+        buf = self._clip_buf
+        return None if buf is None else buf[buf.numel() - 4:buf.numel() - 2]
+
+    def _take_clip(self):
+        """The threshold of THIS update (None: no clipping) -- consumes a one-step arming."""
+        c, self._clip_once = (self._clip_once if self._clip_once is not None else self.max_grad_norm), None
+        return float(c) if (c is not None and c > 0) else None
+
+    def _sqnorm(self, flat_grad):
+        buf = self._clip_buffer(flat_grad.device)
+        _lib.get().call("sed_grad_sqnorm", flat_grad.data_ptr(), flat_grad.numel(), buf.data_ptr(), _lib.stream_ptr(flat_grad))
+        return buf
+
+    def _clip_torch(self, max_norm):
+        """No arena: clip_grad_norm_'s own arithmetic on the parameter list (the norm is of the grad_scale-d gradient); rewrites p.grad."""
+        grads = [p.grad for p in self._group_params() if p.grad is not None]
+        if not grads:
+            return
+        total = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(g, 2.0) for g in grads]), 2.0) * abs(self.grad_scale)
+        coef = torch.clamp(max_norm / (total + 1e-6), max=1.0)
+        for g in grads:
+            g.mul_(coef.to(g.device))
+        buf = self._clip_buffer(grads[0].device)
+        buf[buf.numel() - 4:buf.numel() - 2].copy_(torch.stack([total, coef]))
 
     # ---- a torch.optim.Adam handed in by the recipe (train_sed.py:199-201) --------------------------------------------
     served = False      # set by SEDTask4's whole-step mode: the update of this step() call has already run (inside the closure)
@@ -146,6 +201,7 @@ class FusedAdam(torch.optim.Optimizer):
             return False
         opt.__class__ = cls
         opt._arena_src, opt.grad_scale, opt._flat_state = model, 1.0, None
+        opt.max_grad_norm = opt._clip_once = opt._clip_buf = None
         opt._patch_step_function()          # (what Optimizer.__init__ / __setstate__ do for a class: the profiler-hooked step)
         return True
 
@@ -223,10 +279,17 @@ class FusedAdam(torch.optim.Optimizer):
             self._flat_state = None                 # rebuilt from self.state at the next flat step
 
     # ---- the step -------------------------------------------------------------------------------------------
-    def _launch(self, p, g, m, v, n, group, step, hyper_dev=None):
+    def _launch(self, p, g, m, v, n, group, step, hyper_dev=None, clip=None):
+        """clip: None, or (the buffer sed_grad_sqnorm filled, max_norm) -> sed_adam_step_clipped."""
         b1, b2 = group["betas"]
         bc1 = 1.0 - b1 ** step
         bc2 = 1.0 - b2 ** step
+        if clip is not None:
+            buf, max_norm = clip
+            _lib.get().call("sed_adam_step_clipped", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, float(b1), float(b2),
+                            float(group["eps"]), float(group["lr"] / bc1), float(1.0 / math.sqrt(bc2)), float(self.grad_scale),
+                            hyper_dev, buf.data_ptr(), max_norm, buf.data_ptr() + 4 * (buf.numel() - 4), _lib.stream_ptr(p))
+            return
         _lib.get().call("sed_adam_step", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, float(b1), float(b2),
                         float(group["eps"]), float(group["lr"] / bc1), float(1.0 / math.sqrt(bc2)), float(self.grad_scale),
                         hyper_dev, _lib.stream_ptr(p))
@@ -242,8 +305,10 @@ class FusedAdam(torch.optim.Optimizer):
             self.served = False
             return loss
         arena = self.arena
+        max_norm = self._take_clip()
         if self._flat_ok(arena) and arena.grads_are_flat():
             st = self._flat(arena)
+            clip = (self._sqnorm(arena.flat_grad), max_norm) if max_norm is not None else None
             dyn = _graph.active()
             if dyn is not None:
                 # hipGraph replay: step counter and the two step-dependent factors are host logic re-run every step
@@ -257,11 +322,17 @@ class FusedAdam(torch.optim.Optimizer):
 
                 dyn.host(advance)
                 self._launch(arena.flat, arena.flat_grad, st["m"], st["v"], arena.numel, group, st["step"],
-                             hyper_dev=dyn.ptr(dyn.F_ADAM_STEP))
+                             hyper_dev=dyn.ptr(dyn.F_ADAM_STEP), clip=clip)
                 return loss
             st["step"] += 1
-            self._launch(arena.flat, arena.flat_grad, st["m"], st["v"], arena.numel, self.param_groups[0], st["step"])
+            self._launch(arena.flat, arena.flat_grad, st["m"], st["v"], arena.numel, self.param_groups[0], st["step"], clip=clip)
             return loss
+        clip = None
+        if max_norm is not None:
+            if self._flat_ok(arena):        # gradients outside the (intact) arena: one norm over the gathered copy
+                clip = (self._sqnorm(arena.gather_grads()), max_norm)
+            else:
+                self._clip_torch(max_norm)
         # per-tensor path: continues from whatever moments exist (the flat buffers' views, a loaded state dict, or zeros)
         flat_step = self._flat_state["step"] if self._flat_state is not None else None
         for group in self.param_groups:
@@ -278,7 +349,7 @@ class FusedAdam(torch.optim.Optimizer):
                 if st["exp_avg"].device != p.device:
                     st["exp_avg"], st["exp_avg_sq"] = st["exp_avg"].to(p.device), st["exp_avg_sq"].to(p.device)
                 g = p.grad.contiguous()
-                self._launch(p.data, g, st["exp_avg"], st["exp_avg_sq"], p.numel(), group, step)
+                self._launch(p.data, g, st["exp_avg"], st["exp_avg_sq"], p.numel(), group, step, clip=clip)
         if flat_step is not None:
             self._flat_state["step"] = flat_step + 1
         return loss

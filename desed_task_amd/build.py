@@ -49,6 +49,7 @@ def _stale(target, deps):
 def build(verbose=True, force=False):
     os.makedirs(OBJ, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    headers.append(os.path.join(os.path.dirname(HERE), "include", "sed_hip.h"))      # (sed_optim.hip takes its SED_SQNORM_* constants from it)
     jobs = []
     objs = []
     for src in sources():

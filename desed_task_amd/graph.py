@@ -366,7 +366,7 @@ class GraphedStepDriver:
         if d.side is not None:
             torch.cuda.current_stream().wait_stream(d.side)
         if not d.exchange or self.capture_exchange:
-            d.opt.step()
+            d.step_optimizer()
             task.lr_scheduler_step(d.sched, 0, None)
         _ops.probe("step_end")
         return loss
@@ -384,7 +384,7 @@ class GraphedStepDriver:
         else:
             d.allreduce_grads()
         d._mark("exchange_done")
-        d.opt.step()
+        d.step_optimizer()
         d._mark("adam_done")
         self.task.lr_scheduler_step(d.sched, 0, None)
 

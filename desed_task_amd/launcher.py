@@ -13,6 +13,10 @@ State that diverges across ranks: the student's and the teacher's Ba
 normalises its own clips; momentum 0.99 makes them ~ the last batch).  Policy: `average_bn_buffers(task)` -- ONE all-reduce of
 the 2 x 1 248 floats -- before every validation / test pass and before `save_checkpoint`, which writes from rank 0 only.
 `RankShardedBatchSampler` gives rank r the batches r, r + world, ... of the recipe's ConcatDatasetBatchSampler.
+
+`training.gradient_clip` of the YAML (what the recipes pass to pl.Trainer as gradient_clip_val; 0. in the 2023 files, 5.0 in the 2024
+`confs/pretrained.yaml`) is honoured: the norm of the rank-AVERAGED gradient is clipped inside the fused Adam step
+(arena.FusedAdam.max_grad_norm, set by StepDriver).  `python -m desed_task_amd.launcher` prints the effective value at start-up.
 """
 import os
 
@@ -155,6 +159,16 @@ class StepDriver:
         self._gru_dw_side_arg = bool(gru_dw_side)
         if hasattr(self.opt, "grad_scale"):
             self.opt.grad_scale = 1.0 / world_size
+        # `training.gradient_clip` (Lightning's gradient_clip_val; 2024 confs/pretrained.yaml:17 sets 5.0): norm clipping of the AVERAGED
+        # gradient between the exchange and the update.  arena.FusedAdam does it inside its own launches (max_grad_norm); any other
+        # optimizer gets torch's clip_grad_norm_ in step_optimizer().  0 / None / absent: nothing changes, no launch is added.
+        clip = (task.hparams.get("training") or {}).get("gradient_clip")
+        self.clip = float(clip) if (clip is not None and float(clip) > 0) else None
+        self._torch_clip = None
+        if hasattr(self.opt, "max_grad_norm"):
+            self.opt.max_grad_norm = self.clip
+        else:
+            self._torch_clip = self.clip
         if overlap_allreduce is None:
             # Default: bucket A under the CNN backward.  Exception: with the front half of the next step and the teacher's CNN
             # forward pipelined under this step's backward (prefetch "teacher") the step stays ONE graph -- the side branch must
@@ -326,6 +340,13 @@ class StepDriver:
                     if not hasattr(self.opt, "grad_scale"):
                         p.grad.div_(self.world)
 
+    def step_optimizer(self):
+        """optimizer.step() -- every exchange scheme (blocking, two buckets, captured) ends here, behind `_finish_scale`'s division, so
+        the clipping sees the averaged gradient.  (arena.FusedAdam clips in its own launches.)"""
+        if self._torch_clip is not None:
+            torch.nn.utils.clip_grad_norm_([p for p in self.task.sed_student.parameters() if p.grad is not None], self._torch_clip)
+        self.opt.step()
+
     def _mark(self, tag):
         if self.probe is not None:
             self.probe.mark(tag)
@@ -416,7 +437,7 @@ class StepDriver:
         if self.side is not None:
             torch.cuda.current_stream().wait_stream(self.side)   # Adam overwrites theta_s that the EMA reads
         self._mark("exchange_done")
-        self.opt.step()
+        self.step_optimizer()
         self._mark("adam_done")
         task.lr_scheduler_step(self.sched, 0, None)
         return loss
@@ -810,6 +831,9 @@ def main(argv=None, cpu_test_device=False, entry_module="desed_task_amd.launcher
         return 0
     task = build_run(config, log_dir, rank, world, strong_real=args.strong_real, fast_dev_run=args.fast_dev_run)
     task.to(device)
+    if rank == 0:
+        clip = config["training"].get("gradient_clip") or 0
+        print("gradient_clip: %s" % ("%g (norm of the averaged gradient, clipped inside the fused Adam step)" % clip if clip > 0 else "off"))
     start, best = 0, None
     if args.resume_from_checkpoint:
         ckpt = load_checkpoint(task, args.resume_from_checkpoint, resume=True)

@@ -219,8 +219,7 @@ class SEDTask4(_Base):
             return "the optimizer is not a plain Adam over sed_student.parameters() (arena.FusedAdam.adopt), or there is no scheduler"
         if tr.get("accumulate_batches", 1) != 1:
             return "accumulate_batches != 1 (one optimizer step per training_step is what a whole step is)"
-        if (tr.get("gradient_clip") or 0) > 0:
-            return "gradient_clip > 0 (clipping sits between backward and the optimizer step)"
+        # (gradient_clip > 0 is no blocker: the driver hands it to the adopted FusedAdam, which clips inside its own launches)
         if self._ddp_world() > 1 and os.environ.get("SED_DDP_GRAPH_EXCHANGE") != "1":
             # (with the exchange captured -- SED_DDP_GRAPH_EXCHANGE=1 -- the whole data-parallel step, all-reduce(s) and Adam included,
             #  is the one graph behind training_step and the hooks that follow find their work done, exactly as at world size 1.  Without
@@ -393,10 +392,42 @@ class SEDTask4(_Base):
         for name, value, kw in rec:
             self.log(name, value, **kw)
         self._served = {"ema", "zero_grad", "backward", "scheduler"}
+        if self._driver_clip() is not None:
+            self._served.add("clip")        # (only then: without clipping Lightning never calls configure_gradient_clipping's body)
         self.opt.served = True
         # "0-d loss tensor with grad" (SURVEY 8b): a leaf, so that Lightning's `loss / accumulate_grad_batches` and a hand-written
         # `loss.backward()` both work -- there is nothing left to differentiate
         return loss.detach().requires_grad_(True)
+
+    def _driver_clip(self):
+        """The norm threshold the whole-step driver applies inside its step (None: no clipping)."""
+        drv = self._driver
+        return getattr(getattr(drv, "eager", drv), "clip", None) if drv is not None else None
+
+    def configure_gradient_clipping(self, optimizer, optimizer_idx=0, gradient_clip_val=None, gradient_clip_algorithm=None):
+        """Lightning 1.9 calls this right after on_before_optimizer_step, inside the closure, with the trainer's gradient_clip_val
+        (`training.gradient_clip` in every recipe: train_sed.py:287, train_pretrained.py:461 / 2024 :569).  Whole-step mode: the driver
+        has clipped inside the step it ran.  Otherwise norm clipping on the adopted FusedAdam arms THAT optimizer for the update that
+        follows (same two launches as in the driver, p.grad not rewritten); value clipping and foreign optimizers take Lightning's
+        default (torch.nn.utils.clip_grad_norm_ / clip_grad_value_)."""
+        val = float(gradient_clip_val) if gradient_clip_val else 0.0
+        if self._take("clip"):
+            if val != self._driver_clip() or (gradient_clip_algorithm or "norm") != "norm":
+                raise RuntimeError("the trainer asks for gradient_clip_val=%r (%s) but the whole step clipped the norm at "
+                                   "hparams['training']['gradient_clip'] = %r" % (gradient_clip_val, gradient_clip_algorithm or "norm",
+                                                                                    self._driver_clip()))
+            return
+        if val <= 0:
+            return
+        if isinstance(self.opt, FusedAdam) and self.opt.served:
+            raise RuntimeError("the trainer asks for gradient_clip_val=%r but the whole step has already applied its update without "
+                               "clipping: set hparams['training']['gradient_clip'] to the same value" % (gradient_clip_val,))
+        raw = getattr(optimizer, "_optimizer", optimizer)       # (a LightningOptimizer wraps the optimizer it was given)
+        if (gradient_clip_algorithm or "norm") == "norm" and raw is self.opt and isinstance(raw, FusedAdam):
+            raw.arm_clip(val)
+            return
+        super().configure_gradient_clipping(optimizer, optimizer_idx, gradient_clip_val=gradient_clip_val,
+                                            gradient_clip_algorithm=gradient_clip_algorithm)
 
     def optimizer_zero_grad(self, epoch, batch_idx, optimizer, *args, **kwargs):
         if not self._take("zero_grad"):

@@ -52,7 +52,9 @@ int sed_take_log(const float* x, float* y, long long n, void* stream);
  *   c_dev      (sed_mixup)             : {c, 1-c} (the sentinel c = 2 makes the launch a no-op);
  *   weight_dev (sed_mt_loss)           : consistency-loss weight;
  *   alpha_dev  (sed_ema_update)        : {alpha, 1-alpha};
- *   hyper_dev  (sed_adam_step)         : {step_size, inv_bc2_sqrt}.
+ *   hyper_dev  (sed_adam_step, sed_adam_step_clipped) : {step_size, inv_bc2_sqrt}.
+ * (sed_adam_step_clipped's `partials` is not of this kind: it is the previous launch's output, read on the device every step;
+ *  its max_norm is constant over a run and stays by value.)
  * Null pointers give the plain eager behaviour.  Host side: desed_task_amd/graph.py. */
 
 /* K2: desed_task/data_augm.py:31-51 mixup on a group of n clips of L floats, in place (tmp = scratch copy).
@@ -375,6 +377,27 @@ int sed_ema_update(float* teacher, const float* student, long long n, float alph
 /* torch.optim.Adam step (train_sed.py:199-201) over the whole arena; grad_scale folds in 1/world_size. */
 int sed_adam_step(float* p, const float* g, float* m, float* v, long long n, float b1, float b2, float eps,
                   float step_size, float inv_bc2_sqrt, float grad_scale, const float* hyper_dev, void* stream);
+
+/* ---- gradient-norm clipping: `gradient_clip_val` of the recipes' pl.Trainer (recipes/dcase2024_task4_baseline/train_pretrained.py:569,
+ * confs/pretrained.yaml:17 `gradient_clip: 5.0`) -> Lightning 1.9 -> torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2),
+ * on the flat gradient arena, with no host read-back:  two launches on one stream, the kernel boundary is the hand-over. */
+#define SED_SQNORM_THREADS 256        /* lanes of a workgroup of sed_grad_sqnorm */
+#define SED_SQNORM_MAX_PARTIALS 256   /* floats of `partials`; workgroups G = min(this, max(1, ceil((n / 4) / SED_SQNORM_THREADS))) */
+
+/* partials[0 .. SED_SQNORM_MAX_PARTIALS) = per-workgroup sums of g[i]^2 over n floats; slots G and above are written as 0, so the
+ * consumer always adds the same count.  Addition order (fixed: same bits every run, and G depends on n only): lane t of workgroup
+ * b takes the float4s (k G + b) SED_SQNORM_THREADS + t, k = 0, 1, ..., and adds x^2, y^2, z^2, w^2 in turn (one FMA each) -- lane 0
+ * of workgroup 0 then the n % 4 tail elements --; 6 butterfly levels over the wave; ((w0 + w1) + w2) + w3 over the four waves.
+ * g is only read.  n >= 4: g 16-byte aligned (float4 loads), else SED_ERR_ARG; n < 4 is legal at any alignment. */
+int sed_grad_sqnorm(const float* g, long long n, float* partials, void* stream);
+
+/* sed_adam_step consuming g * grad_scale * coef:  total = |grad_scale| sqrt(sum of the partials), the partials added by every
+ * workgroup in the order above (one per lane, butterfly, four waves);  coef = min(1, max_norm / (total + 1e-6)) in fp32, a NaN total
+ * gives a NaN coef (torch.clamp).  clip_out[0 .. 2) = {total, coef}.  coef == 1 gives sed_adam_step's result bit for bit.
+ * `partials` must come from sed_grad_sqnorm over the same g, earlier on the same stream. */
+int sed_adam_step_clipped(float* p, const float* g, float* m, float* v, long long n, float b1, float b2, float eps,
+                          float step_size, float inv_bc2_sqrt, float grad_scale, const float* hyper_dev, const float* partials,
+                          float max_norm, float* clip_out, void* stream);
 
 /* Zero up to four small accumulator buffers in one launch (null / 0 entries are skipped).  Counts are indexed as int:
  * a count above 2^31 - 256 is SED_ERR_UNSUPPORTED and nothing is zeroed. */

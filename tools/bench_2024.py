@@ -1,7 +1,10 @@
 """Throughput of the 2024 recipe's training step (BASELINE config 4's CRNN half) at the recipe's own sizes:
 `recipes/dcase2024_task4_baseline/confs/pretrained.yaml` -- batch [12, 6, 6, 12, 24] = 60 clips of 10 s, 27 classes, n_RNN_cell 192,
 dropout 0.5, dropstep_recurrent 0.3 x 16, frozen 768 x 496 embeddings per clip, mixup on features and embeddings, class masks --
-random weights, synthetic data.  Secondary workload: not the headline metric of bench.py.   python tools/bench_2024.py [--graph]"""
+random weights, synthetic data.  Secondary workload: not the headline metric of bench.py.
+    python tools/bench_2024.py [--graph] [--prefetch] [--gradient-clip X]
+--gradient-clip X: `training.gradient_clip` (confs/pretrained.yaml:17 ships 5.0) -- norm clipping inside the fused optimizer step; the
+JSON line then carries the last step's {norm, coef} (arena.FusedAdam.last_clip)."""
 import json, os, random, sys, time
 sys.path.insert(0, ".")
 import numpy as np
@@ -21,6 +24,8 @@ config["training"].update(batch_size=list(BS), mixup="soft", mixup_prob=0.5, epo
 config["net"].update(dropout=0.5, rnn_layers=1, nclass=NCLASS, n_RNN_cell=192, dropstep_recurrent=0.3, dropstep_recurrent_len=16,
                      use_embeddings=True, embedding_size=768, embedding_type="frame", aggregation_type="pool1d")
 config["pretrained"] = {"e2e": False, "freezed": True, "model": "beats"}
+if "--gradient-clip" in sys.argv:
+    config["training"]["gradient_clip"] = float(sys.argv[sys.argv.index("--gradient-clip") + 1])
 student = CRNN(**config["net"]).to(dev)
 opt = FusedAdam(student.parameters(), lr=1e-3, betas=(0.9, 0.999), arena=student.arena)
 sched = {"scheduler": ExponentialWarmup(opt, 1e-3, 50 * 118), "interval": "step"}
@@ -102,6 +107,8 @@ clips_s = B / dt
 print(json.dumps({"workload": "dcase2024 pretrained.yaml training step: batch 60 = [12,6,6,12,24] x 10 s, 27 classes, n_RNN_cell 192, "
                               "768 x 496 embeddings per clip, dropout + dropstep + mixup on", "launch": "hipGraph" if "--graph" in sys.argv else "eager",
                   "front_end": "pipelined (teacher)" if pipelined else "inline",
+                  "gradient_clip": config["training"].get("gradient_clip"),
+                  "last_clip": [float(x) for x in opt.last_clip.cpu()] if opt.last_clip is not None else None,
                   "ms_per_step": round(dt * 1e3, 3), "clips_per_s": round(B / dt, 1), "loss": round(float(loss), 5),
                   "step_roofline": {"mfma_tflops": round(6.464e9 * clips_s / 1e12, 2),
                                     "mfma_frac_of_bf16_peak": round(6.464e9 * clips_s / (PEAK_BF16_MFMA_TFLOPS * 1e12), 5),
