@@ -278,6 +278,14 @@ __device__ __forceinline__ float sed_row16_sum(float v) {
     v += sed_row_ror4(v); v += sed_row_ror8(v);
     return v;
 }
+// lane i of every group of 8 lanes takes the value of lane 7 - i (row_half_mirror); behind sed_quad_sum that is the OTHER quad's sum
+__device__ __forceinline__ float sed_half_mirror(float v) {
+#ifdef SED_EMU
+    return __shfl_xor(v, 7);
+#else
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
+#endif
+}
 // sum over the four lanes of a quad, result in all four
 __device__ __forceinline__ float sed_quad_sum(float v) {
     v += sed_quad_xor1(v);

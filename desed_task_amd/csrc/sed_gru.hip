@@ -525,6 +525,163 @@ __global__ __launch_bounds__(4 * H) void gru_fwd_kernel(const float* __restrict_
         for (int i = tid; i < 2 * 32 * 8; i += NT_) gru_stamp_buf[i] = (&s_ts[0][0][0])[i];
 #endif
 }
+// ---------------------------------------------------------------------------------------------
+// H = 256 (the widest n_RNN_cell of the 2024 recipe's search): W_hh of one direction is 768 KB -- more than a CU's registers
+// (512 KB) and LDS (160 KB) hold beside the state -- so a share of it is re-read from L2 every step.
+// 1024 threads = 4 waves per SIMD = 128 VGPRs; thread (unit j, quarter q) owns the K range k = 16 kb + 4 q .. + 3, kb = 0 .. 15 (the
+// four lanes of a quad read 64 contiguous bytes of a W_hh row and of the hidden state).  Its 3 x 16 weight float4s are numbered
+// f = 3 kb + g (gate g); NS of the 48, evenly spread over f, are STREAMED, the first NR of the rest live in registers and the last
+// NL in LDS ([block][thread] float4).  The streamed ones go through a ring of RD float4 registers: using element e frees its slot
+// for element (e + RD) mod NS, so RD loads are always in flight -- over the FMAs, the gates and the barrier, into the next step
+// (they do not depend on the hidden state).  Loads only: no store is issued inside the step loop, see above.
+// ---------------------------------------------------------------------------------------------
+#define GRU_S_H 256
+#define GRU_S_NB 48                                                  // weight float4s per thread: 3 gates x 16
+__host__ __device__ constexpr int gru_s_nstream(int f, int ns) { return f * ns / GRU_S_NB; }          // streamed blocks among 0 .. f - 1
+__host__ __device__ constexpr bool gru_s_streamed(int f, int ns) { return gru_s_nstream(f + 1, ns) > gru_s_nstream(f, ns); }
+__host__ __device__ constexpr int gru_s_block(int e, int ns) { return (GRU_S_NB * (e + 1) + ns - 1) / ns - 1; }   // block of streamed element e
+// <CH, NR, NL, NS, RD>: steps per staging chunk, weight float4s in registers / in LDS / streamed, ring depth
+#define GRU_S_FWD_CH 2
+#define GRU_S_FWD_NL 7
+#define GRU_S_FWD GRU_S_FWD_CH, 13, GRU_S_FWD_NL, 28, 4
+#define GRU_S_BWD_CH 2
+#define GRU_S_BWD_NL 6
+#define GRU_S_BWD GRU_S_BWD_CH, 10, GRU_S_BWD_NL, 32, 4
+template <int CH, int NR, int NL, int NS, int RD>
+__global__ __launch_bounds__(4 * GRU_S_H) void gru_fwd_stream_kernel(const float* __restrict__ gi, const float* __restrict__ whh0,
+                                                                     const float* __restrict__ whh1, const float* __restrict__ bhh0,
+                                                                     const float* __restrict__ bhh1, float* __restrict__ out,
+                                                                     float* __restrict__ saved, int B, int T) {
+    sed_wave_prio_high();
+    constexpr int H = GRU_S_H, NT_ = 4 * H, NB = GRU_S_NB;
+    static_assert(NR + NL + NS == NB && NS % RD == 0, "ring slot of element e is e mod RD in every step");
+    constexpr int OBP = H + 8, OBS = 5 * OBP;                       // result planes h | r | z | n | hn, the quad's stores 8 banks apart
+    constexpr int GI_F = CH * 3 * H, OB_F = CH * OBS;
+    __shared__ __attribute__((aligned(16))) float hbuf[2][H];
+    SED_DYN_SMEM(smem);
+    float* gis = (float*)smem;                 // [2][CH][3H]
+    float* obuf = gis + 2 * GI_F;              // [2][CH][5][OBP]
+    float4* wls = (float4*)(obuf + 2 * OB_F);  // [NL][NT_]
+    const int tid = threadIdx.x, j = tid >> 2, q = tid & 3;
+    const int b = blockIdx.x >> 1, dir = blockIdx.x & 1;
+    const float* W = dir ? whh1 : whh0;
+    const float* bhh = dir ? bhh1 : bhh0;
+    const float* Wg[3] = {W, W + H * H, W + 2 * H * H};
+    int wo = j * H + 4 * q;                                          // this thread's offset inside a gate's (H, H) block
+    f32x2 wreg[2 * NR];
+    f32x2 ring[2 * RD];
+#pragma unroll
+    for (int f = 0; f < NB; ++f) {
+        const int e = gru_s_nstream(f, NS), r = f - e;
+        if (gru_s_streamed(f, NS) && e >= RD) continue;
+        const float4 w4 = *(const float4*)(Wg[f % 3] + wo + 16 * (f / 3));
+        if (gru_s_streamed(f, NS)) { ring[2 * e] = f32x2{w4.x, w4.y}; ring[2 * e + 1] = f32x2{w4.z, w4.w}; }
+        else if (r < NR) { wreg[2 * r] = f32x2{w4.x, w4.y}; wreg[2 * r + 1] = f32x2{w4.z, w4.w}; }
+        else wls[(r - NR) * NT_ + tid] = w4;
+    }
+    float br = bhh[j], bz = bhh[H + j], bn = bhh[2 * H + j];
+#pragma unroll
+    for (int r = 0; r < 2 * NR; ++r) sed_pin(wreg[r]);
+#pragma unroll
+    for (int e = 0; e < 2 * RD; ++e) sed_pin(ring[e]);
+    sed_pin(br); sed_pin(bz); sed_pin(bn);
+    if (tid < H) hbuf[0][tid] = 0.f;
+    float hprev = 0.f;
+    const int nchunks = (T + CH - 1) / CH;
+    constexpr int GV = (GI_F / 4 + NT_ - 1) / NT_;
+    float4 greg[GV];
+    auto load_chunk = [&](int c) {
+#pragma unroll
+        for (int u = 0; u < GV; ++u) {
+            const int e4 = tid + NT_ * u, s = e4 / (3 * H / 4), p = e4 - s * (3 * H / 4);
+            const int step = c * CH + s;
+            greg[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (e4 < GI_F / 4 && step < T) {
+                const int t = dir ? T - 1 - step : step;
+                greg[u] = *(const float4*)(gi + (((size_t)b * T + t) * 2 + dir) * 3 * H + 4 * p);
+            }
+        }
+    };
+    auto park_chunk = [&](int c) {
+#pragma unroll
+        for (int u = 0; u < GV; ++u)
+            if (tid + NT_ * u < GI_F / 4) *(float4*)(gis + (c & 1) * GI_F + 4 * (tid + NT_ * u)) = greg[u];
+    };
+    auto flush_chunk = [&](int c) {
+        constexpr int PER = 5 * H / 4;
+        const float* ob = obuf + (c & 1) * OB_F;
+        for (int e4 = tid; e4 < CH * PER; e4 += NT_) {
+            const int s = e4 / PER, p = e4 - s * PER;
+            const int step = c * CH + s;
+            if (step >= T) break;
+            const int t = dir ? T - 1 - step : step;
+            const float4 v = *(const float4*)(ob + s * OBS + (p / (H / 4)) * OBP + 4 * (p % (H / 4)));
+            if (p < H / 4) *(float4*)(out + ((size_t)b * T + t) * 2 * H + dir * H + 4 * p) = v;
+            else if (saved) *(float4*)(saved + (((size_t)b * T + t) * 2 + dir) * 4 * H + 4 * (p - H / 4)) = v;
+        }
+    };
+    load_chunk(0);
+    park_chunk(0);
+    __syncthreads();
+    int cur = 0;
+    for (int c = 0; c < nchunks; ++c) {
+        if (c + 1 < nchunks) load_chunk(c + 1);
+        if (c > 0) flush_chunk(c - 1);
+        const float* gch = gis + (c & 1) * GI_F;
+        float* och = obuf + (c & 1) * OB_F;
+        const int nsteps = min(CH, T - c * CH);
+        for (int s = 0; s < nsteps; ++s) {
+            sed_opaque(wo);                    // (the streamed weights are loop-invariant loads: keeps them from being hoisted into 96 registers)
+            const float gr = gch[s * 3 * H + j], gz = gch[s * 3 * H + H + j], gn = gch[s * 3 * H + 2 * H + j];
+            f32x2 acc[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
+            const float* hq = hbuf[cur] + 4 * q;
+#pragma unroll
+            for (int kb = 0; kb < 16; ++kb) {
+                const float4 h4 = *(const float4*)(hq + 16 * kb);
+                const f32x2 lo2 = {h4.x, h4.y}, hi2 = {h4.z, h4.w};
+#pragma unroll
+                for (int g = 0; g < 3; ++g) {
+                    const int f = 3 * kb + g, e = gru_s_nstream(f, NS), r = f - e;
+                    f32x2 w0, w1;
+                    if (gru_s_streamed(f, NS)) {
+                        w0 = ring[2 * (e % RD)]; w1 = ring[2 * (e % RD) + 1];
+                    } else if (r < NR) {
+                        w0 = wreg[2 * (r < NR ? r : 0)]; w1 = wreg[2 * (r < NR ? r : 0) + 1];
+                    } else {
+                        const float4 w4 = wls[(r - NR) * NT_ + tid];
+                        w0 = f32x2{w4.x, w4.y}; w1 = f32x2{w4.z, w4.w};
+                    }
+                    acc[g] = pk_fma(w0, lo2, acc[g]);
+                    acc[g] = pk_fma(w1, hi2, acc[g]);
+                    if (gru_s_streamed(f, NS)) {
+                        // the freed slot takes element e + RD (of the NEXT step behind the last ones: same weights every step)
+                        const int fn = gru_s_block((e + RD) % NS, NS);
+                        const float4 w4 = *(const float4*)(Wg[fn % 3] + wo + 16 * (fn / 3));
+                        ring[2 * (e % RD)] = f32x2{w4.x, w4.y}; ring[2 * (e % RD) + 1] = f32x2{w4.z, w4.w};
+                    }
+                }
+                sed_sched_fence();             // one h block's reads, FMAs and refills at a time (registers)
+            }
+            float ar = acc[0].x + acc[0].y, az = acc[1].x + acc[1].y, an = acc[2].x + acc[2].y;
+            ar = sed_quad_sum(ar); az = sed_quad_sum(az); an = sed_quad_sum(an);
+            const float r = sed_fast_sigmoid(gr + ar + br);
+            const float z = sed_fast_sigmoid(gz + az + bz);
+            const float hn = an + bn;
+            const float n = sed_fast_tanh(gn + r * hn);
+            const float hnew = (1.0f - z) * n + z * hprev;
+            hprev = hnew;
+            // every lane of the quad stores one of the five results (all four hold them)
+            float* o = och + s * OBS;
+            o[q * OBP + j] = q == 0 ? hnew : q == 1 ? r : q == 2 ? z : n;
+            if (q == 0) { hbuf[cur ^ 1][j] = hnew; o[4 * OBP + j] = hn; }
+            cur ^= 1;
+            __syncthreads();
+        }
+        if (c + 1 < nchunks) park_chunk(c + 1);
+        __syncthreads();
+    }
+    flush_chunk(nchunks - 1);
+}
 // A recurrence workgroup claims (most of) its CU's LDS: a (clip, direction) is one latency-bound dependent chain, and any workgroup
 // of another stream that lands on the same CU (the prefetched mel front-end: 24 KB of LDS each, the other model's head, the
 // weight-gradient GEMMs) takes issue slots from it.  With sed_set_tuning(SED_TUNE_GRU_LDS_KB, kb) the launch asks for kb KB of dynamic
@@ -538,8 +695,15 @@ static inline int gru_lds_claim(int smem) {
 
 SED_API int sed_gru_fwd(const float* gi, const float* whh0, const float* whh1, const float* bhh0, const float* bhh1,
                            float* out, float* saved, int B, int T, int H, void* stream) {
-    if (H != 128 && H != 192) return SED_ERR_UNSUPPORTED;
+    if (H != 128 && H != 192 && H != 256) return SED_ERR_UNSUPPORTED;
     if (B <= 0 || T <= 0) return SED_OK;
+    if (H == 256) {
+        int smem = (2 * GRU_S_FWD_CH * 3 * H + 2 * GRU_S_FWD_CH * 5 * (H + 8)) * 4 + GRU_S_FWD_NL * 4 * H * 16;
+        smem = gru_lds_claim(smem);
+        SED_MAX_SMEM((gru_fwd_stream_kernel<GRU_S_FWD>), smem);
+        SED_LAUNCH((gru_fwd_stream_kernel<GRU_S_FWD>), dim3(2 * B), dim3(4 * H), smem, (hipStream_t)stream, gi, whh0, whh1, bhh0, bhh1, out, saved, B, T);
+        return sed_check_launch();
+    }
 #define GRU_FWD_CASE(h, ch)                                                                                                       \
     if (H == h) {                                                                                                                 \
         int smem = (2 * ch * 3 * h + 2 * ch * 5 * (GRU_QSTORE ? h + 8 : h)) * 4 + (h <= 128 ? 0 : 8 * 4 * h * 16);               \
@@ -721,6 +885,174 @@ __global__ __launch_bounds__(4 * H) void gru_bwd_kernel(const float* __restrict_
         if (half == 1) { rec[3 * H + k] = sb_r; rec[4 * H + k] = sb_z; rec[5 * H + k] = sb_hn; }
     }
 }
+// The backward recurrence at H = 256: the structure of gru_bwd_kernel with the weight placement of gru_fwd_stream_kernel.  W_hh^T is
+// read along ROWS of W_hh, a streamed block is one 16-byte load, and a wave's load covers WHOLE 128-byte lines: lane l of wave w owns
+// the unit group grp = 8 (w % 8) + l / 8 (units 4 grp .. + 3: eight groups = 128 contiguous bytes of a row) and the row slice
+// sl = l % 8 + 8 (w / 8), i.e. the gate rows j = 16 jb + sl; block f = 3 jb + g = W[g H + j][4 grp .. + 3] times the ONE gate-vector
+// element j.  (Measured against two other maps -- four dword loads per block; 16 slices in one DPP row = 16 rows x 64 bytes per wave
+// load -- all three run the launch in 2.2 ms: profiles/rnn256.md.)  The 16 slices of a unit group are 8 lanes (two DPP adds in the quad + one
+// row_half_mirror) in each of two waves; the two halves meet in LDS (`psum`, a second barrier per step) and are added in a fixed
+// order by the element-wise part, which keeps gru_bwd_kernel's map: unit k = tid / 4, `half` = tid % 4 picks the plane a lane stores.
+template <int CH, int NR, int NL, int NS, int RD>
+__global__ __launch_bounds__(4 * GRU_S_H) void gru_bwd_stream_kernel(const float* __restrict__ dout, const float* __restrict__ out,
+                                                                     const float* __restrict__ saved, const float* __restrict__ whh0,
+                                                                     const float* __restrict__ whh1, float* __restrict__ dgi,
+                                                                     float* __restrict__ dgh, float* __restrict__ hprev_out,
+                                                                     float* __restrict__ bpart, int B, int T) {
+    sed_wave_prio_high();
+    constexpr int H = GRU_S_H, NT_ = 4 * H, NB = GRU_S_NB;
+    static_assert(NR + NL + NS == NB && NS % RD == 0, "ring slot of element e is e mod RD in every step");
+    constexpr int GP = H + 8;                                        // planes da_r | da_z | dhn: the quad's three stores 8 banks apart
+    constexpr int OBP = H + 8, OBS = 7 * OBP;
+    constexpr int IB_F = CH * 6 * H, OB_F = CH * OBS;
+    __shared__ __attribute__((aligned(16))) float gbuf[2][3 * GP];
+    SED_DYN_SMEM(smem);
+    float* ibuf = (float*)smem;                // [2][CH][6H] = r | z | n | hn | hprev | dout
+    float* obuf = ibuf + 2 * IB_F;             // [2][CH][7][OBP] = dgi(r, z, n) | hprev | dgh(r, z, hn)
+    float4* wls = (float4*)(obuf + 2 * OB_F);  // [NL][NT_]
+    __shared__ __attribute__((aligned(16))) float psum[2][H];
+    const int tid = threadIdx.x, k = tid >> 2, half = tid & 3;
+    const int lane = tid & 63, wv = tid >> 6, grp = 8 * (wv & 7) + (lane >> 3), sl = (lane & 7) + 8 * (wv >> 3);
+    const int b = blockIdx.x >> 1, dir = blockIdx.x & 1;
+    const float* W = dir ? whh1 : whh0;
+    const float* Wg[3] = {W, W + H * H, W + 2 * H * H};
+    int wo = sl * H + 4 * grp;
+    auto wload = [&](int f) { return *(const float4*)(Wg[f % 3] + wo + 16 * (f / 3) * H); };
+    f32x2 wreg[2 * NR];
+    f32x2 ring[2 * RD];
+#pragma unroll
+    for (int f = 0; f < NB; ++f) {
+        const int e = gru_s_nstream(f, NS), r = f - e;
+        if (gru_s_streamed(f, NS) && e >= RD) continue;
+        const float4 w4 = wload(f);
+        if (gru_s_streamed(f, NS)) { ring[2 * e] = f32x2{w4.x, w4.y}; ring[2 * e + 1] = f32x2{w4.z, w4.w}; }
+        else if (r < NR) { wreg[2 * r] = f32x2{w4.x, w4.y}; wreg[2 * r + 1] = f32x2{w4.z, w4.w}; }
+        else wls[(r - NR) * NT_ + tid] = w4;
+    }
+#pragma unroll
+    for (int r = 0; r < 2 * NR; ++r) sed_pin(wreg[r]);
+#pragma unroll
+    for (int e = 0; e < 2 * RD; ++e) sed_pin(ring[e]);
+    const int nchunks = (T + CH - 1) / CH;
+    constexpr int IV = (IB_F / 4 + NT_ - 1) / NT_;
+    float4 ireg[IV];
+    // chunk c covers reverse-order positions rs = c*CH .. c*CH+CH-1, forward step index = T-1-rs
+    auto load_chunk = [&](int c) {
+#pragma unroll
+        for (int u = 0; u < IV; ++u) {
+            const int e4 = tid + NT_ * u, s = e4 / (6 * H / 4), p = e4 - s * (6 * H / 4);
+            const int rs = c * CH + s;
+            ireg[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (e4 < IB_F / 4 && rs < T) {
+                const int step = T - 1 - rs;
+                const int t = dir ? T - 1 - step : step, tp = dir ? t + 1 : t - 1;
+                const size_t bt = (size_t)b * T + t;
+                if (p < H) ireg[u] = *(const float4*)(saved + (bt * 2 + dir) * 4 * H + 4 * p);
+                else if (p < H + H / 4) { if (step > 0) ireg[u] = *(const float4*)(out + ((size_t)b * T + tp) * 2 * H + dir * H + 4 * (p - H)); }
+                else ireg[u] = *(const float4*)(dout + bt * 2 * H + dir * H + 4 * (p - H - H / 4));
+            }
+        }
+    };
+    auto park_chunk = [&](int c) {
+#pragma unroll
+        for (int u = 0; u < IV; ++u)
+            if (tid + NT_ * u < IB_F / 4) *(float4*)(ibuf + (c & 1) * IB_F + 4 * (tid + NT_ * u)) = ireg[u];
+    };
+    auto flush_chunk = [&](int c) {
+        constexpr int PER = 7 * H / 4;
+        const float* ob = obuf + (c & 1) * OB_F;
+        for (int e4 = tid; e4 < CH * PER; e4 += NT_) {
+            const int s = e4 / PER, p = e4 - s * PER;
+            const int rs = c * CH + s;
+            if (rs >= T) break;
+            const int step = T - 1 - rs;
+            const int t = dir ? T - 1 - step : step;
+            const size_t bt = (size_t)b * T + t;
+            const int pl = p / (H / 4), w4 = 4 * (p - pl * (H / 4));
+            const float4 v = *(const float4*)(ob + s * OBS + pl * OBP + w4);
+            if (pl < 3) *(float4*)(dgi + (bt * 2 + dir) * 3 * H + pl * H + w4) = v;
+            else if (pl == 3) *(float4*)(hprev_out + (bt * 2 + dir) * H + w4) = v;
+            else *(float4*)(dgh + (bt * 2 + dir) * 3 * H + (pl - 4) * H + w4) = v;
+        }
+    };
+    load_chunk(0);
+    park_chunk(0);
+    __syncthreads();
+    float dh_carry = 0.f;
+    float sb_r = 0.f, sb_z = 0.f, sb_n = 0.f, sb_hn = 0.f;     // bias gradients: sums over this clip's steps (off the chain)
+    int cur = 0;
+    for (int c = 0; c < nchunks; ++c) {
+        if (c + 1 < nchunks) load_chunk(c + 1);
+        if (c > 0) flush_chunk(c - 1);
+        const float* ich = ibuf + (c & 1) * IB_F;
+        float* och = obuf + (c & 1) * OB_F;
+        const int nsteps = min(CH, T - c * CH);
+        for (int s = 0; s < nsteps; ++s) {
+            sed_opaque(wo);                    // (see the forward)
+            const float* in = ich + s * 6 * H;
+            const float r = in[k], z = in[H + k], n = in[2 * H + k], hn = in[3 * H + k], hp = in[4 * H + k];
+            const float dh = in[5 * H + k] + dh_carry;
+            const float dn = dh * (1.0f - z);
+            const float dzg = dh * (hp - n);
+            const float da_n = dn * (1.0f - n * n);
+            const float da_z = dzg * z * (1.0f - z);
+            const float da_r = da_n * hn * r * (1.0f - r);
+            const float dhn = da_n * r;
+            sb_r += da_r; sb_z += da_z; sb_n += da_n; sb_hn += dhn;
+            float* o = och + s * OBS;
+            // all four lanes of the quad hold the same values: three store instructions on the chain instead of ten
+            const float g3 = half == 0 ? da_r : half == 1 ? da_z : dhn;
+            if (half < 3) gbuf[cur][half * GP + k] = g3;
+            o[half * OBP + k] = half == 0 ? da_r : half == 1 ? da_z : half == 2 ? da_n : hp;
+            if (half < 3) o[(4 + half) * OBP + k] = g3;
+            __syncthreads();
+            const float* gv = gbuf[cur] + sl;
+            f32x2 acc[3][2] = {{{0.f, 0.f}, {0.f, 0.f}}, {{0.f, 0.f}, {0.f, 0.f}}, {{0.f, 0.f}, {0.f, 0.f}}};     // a chain per gate, units (0, 1) | (2, 3)
+#pragma unroll
+            for (int jb = 0; jb < 16; ++jb) {
+#pragma unroll
+                for (int g = 0; g < 3; ++g) {
+                    const int f = 3 * jb + g, e = gru_s_nstream(f, NS), rr = f - e;
+                    const float gj = gv[g * GP + 16 * jb];
+                    const f32x2 g2 = {gj, gj};
+                    f32x2 w0, w1;
+                    if (gru_s_streamed(f, NS)) {
+                        w0 = ring[2 * (e % RD)]; w1 = ring[2 * (e % RD) + 1];
+                    } else if (rr < NR) {
+                        w0 = wreg[2 * (rr < NR ? rr : 0)]; w1 = wreg[2 * (rr < NR ? rr : 0) + 1];
+                    } else {
+                        const float4 w4 = wls[(rr - NR) * NT_ + tid];
+                        w0 = f32x2{w4.x, w4.y}; w1 = f32x2{w4.z, w4.w};
+                    }
+                    acc[g][0] = pk_fma(w0, g2, acc[g][0]);
+                    acc[g][1] = pk_fma(w1, g2, acc[g][1]);
+                    if (gru_s_streamed(f, NS)) {
+                        const float4 w4 = wload(gru_s_block((e + RD) % NS, NS));
+                        ring[2 * (e % RD)] = f32x2{w4.x, w4.y}; ring[2 * (e % RD) + 1] = f32x2{w4.z, w4.w};
+                    }
+                }
+                sed_sched_fence();
+            }
+            const f32x2 a01 = (acc[0][0] + acc[1][0]) + acc[2][0], a23 = (acc[0][1] + acc[1][1]) + acc[2][1];
+            float a0 = sed_quad_sum(a01.x), a1 = sed_quad_sum(a01.y), a2 = sed_quad_sum(a23.x), a3 = sed_quad_sum(a23.y);
+            a0 += sed_half_mirror(a0); a1 += sed_half_mirror(a1); a2 += sed_half_mirror(a2); a3 += sed_half_mirror(a3);
+            if ((lane & 7) == 0) *(float4*)(psum[wv >> 3] + 4 * grp) = make_float4(a0, a1, a2, a3);
+            __syncthreads();                   // (the next write of psum sits behind the next step's first barrier)
+            dh_carry = dh * z + (psum[0][k] + psum[1][k]);
+            cur ^= 1;
+        }
+        __syncthreads();                       // all steps of the chunk done (gbuf/obuf/ibuf reads retired)
+        if (c + 1 < nchunks) park_chunk(c + 1);
+        __syncthreads();
+    }
+    flush_chunk(nchunks - 1);
+    // this (clip, direction)'s record [db_ih (3H) | db_hh (3H)], as gru_bwd_kernel leaves it
+    if (bpart != nullptr) {
+        float* rec = bpart + (size_t)blockIdx.x * 6 * H;
+        if (half == 0) { rec[k] = sb_r; rec[H + k] = sb_z; rec[2 * H + k] = sb_n; }
+        if (half == 1) { rec[3 * H + k] = sb_r; rec[4 * H + k] = sb_z; rec[5 * H + k] = sb_hn; }
+    }
+}
 // bias gradients: out[dir][j] = sum over clips b of bpart[2 b + dir][j] in clip order, j < 6H = db_ih (3H) | db_hh (3H)
 __global__ __launch_bounds__(256) void gru_bias_reduce_kernel(const float* __restrict__ bpart, float* __restrict__ dbi0,
                                                               float* __restrict__ dbi1, float* __restrict__ dbh0,
@@ -743,7 +1075,7 @@ __global__ __launch_bounds__(256) void gru_bias_reduce_kernel(const float* __res
 SED_API int sed_gru_bwd(const float* dout, const float* out, const float* saved, const float* whh0, const float* whh1,
                            float* dgi, float* dgh, float* hprev, float* dbi0, float* dbi1, float* dbh0, float* dbh1, int B, int T,
                            int H, float* scratch, void* stream) {
-    if (H != 128 && H != 192) return SED_ERR_UNSUPPORTED;
+    if (H != 128 && H != 192 && H != 256) return SED_ERR_UNSUPPORTED;
     if ((dbi0 == nullptr) != (dbi1 == nullptr) || (dbh0 == nullptr) != (dbh1 == nullptr)) return SED_ERR_ARG;
     const bool want_bias = dbi0 || dbh0;
     if (B <= 0 || T <= 0) {
@@ -752,6 +1084,13 @@ SED_API int sed_gru_bwd(const float* dout, const float* out, const float* saved,
     }
     if (want_bias && scratch == nullptr) return SED_ERR_ARG;
     float* bpart = scratch;                       // (scratch without bias pointers: records only, summed later by sed_gru_bias_reduce)
+    if (H == 256) {
+        int smem = (2 * GRU_S_BWD_CH * 6 * H + 2 * GRU_S_BWD_CH * 7 * (H + 8)) * 4 + GRU_S_BWD_NL * 4 * H * 16;
+        smem = gru_lds_claim(smem);
+        SED_MAX_SMEM((gru_bwd_stream_kernel<GRU_S_BWD>), smem);
+        SED_LAUNCH((gru_bwd_stream_kernel<GRU_S_BWD>), dim3(2 * B), dim3(4 * H), smem, (hipStream_t)stream, dout, out, saved, whh0, whh1, dgi, dgh,
+                   hprev, bpart, B, T);
+    }
 #define GRU_BWD_CASE(h, ch)                                                                                                       \
     if (H == h) {                                                                                                                 \
         int smem = (2 * ch * 6 * h + 2 * ch * 7 * (GRU_QSTORE ? h + 8 : h)) * 4 + (h <= 128 ? 0 : 8 * 4 * h * 16);               \
@@ -771,7 +1110,7 @@ SED_API int sed_gru_bwd(const float* dout, const float* out, const float* saved,
 // The second half of sed_gru_bwd on its own: the bias gradients from the records a sed_gru_bwd call WITHOUT bias pointers left in
 // `scratch`.  Nothing on the backward chain reads them (the optimizer does), so a caller can run this beside the chain.
 SED_API int sed_gru_bias_reduce(const float* scratch, float* dbi0, float* dbi1, float* dbh0, float* dbh1, int B, int H, void* stream) {
-    if (H != 128 && H != 192) return SED_ERR_UNSUPPORTED;
+    if (H != 128 && H != 192 && H != 256) return SED_ERR_UNSUPPORTED;
     if ((dbi0 == nullptr) != (dbi1 == nullptr) || (dbh0 == nullptr) != (dbh1 == nullptr)) return SED_ERR_ARG;
     if (!dbi0 && !dbh0) return SED_OK;
     if (B <= 0) { sed_zero4((hipStream_t)stream, dbi0, dbi0 ? 3 * H : 0, dbi1, dbi1 ? 3 * H : 0, dbh0, dbh0 ? 3 * H : 0, dbh1, dbh1 ? 3 * H : 0); return SED_OK; }

@@ -4,7 +4,7 @@
 //  loss : recipes/dcase2023_task4_baseline/local/sed_trainer.py:309-342 -- BCE (strong on the first n_strong
 //         clips, weak on the next n_weak), the two teacher BCEs (logging), MSE student-vs-teacher on all clips;
 //         emits the scalars and the gradient seeds d(total)/d(strong_s), d(total)/d(weak_s).
-// Layout: x (B,T,D), D = 2 * n_RNN_cell = 256 (2023 recipe) or 384 (2024 recipe); strong/sof (B,T,NC) (the Python side returns the (B,NC,T) transposed view);
+// Layout: x (B,T,D), D = 2 * n_RNN_cell = 256 (2023 recipe), 384 (2024 recipe) or 512; strong/sof (B,T,NC) (the Python side returns the (B,NC,T) transposed view);
 // labels stay in the reference layout (B,NC,T).
 #include "sed_common.h"
 
@@ -115,6 +115,125 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(const float* __r
         weak[b * NC + tid] = (cvalid && !cvalid[b * NC + tid]) ? 0.f : n / d;
         den[b * NC + tid] = d;
     }
+}
+// D = 512 (n_RNN_cell 256) runs 512 threads per clip: two waves per SIMD = 256 registers, so the 4 x 27 per-class values of a
+// thread stay in registers (at 1024 threads the 27-class instantiations spill 98); 128 frames per pass.  head_fwd_body is
+// head_fwd_kernel's body with the thread count as a parameter; the 1024-thread kernel above keeps its own text, because it is on the
+// benchmarked path and folding it into the shared body moved its instructions.
+#define HEAD_THREADS_WIDE 512
+template <int NC, int D, int NTH>
+__device__ __forceinline__ void head_fwd_body(const float* __restrict__ x, const float* __restrict__ W1,
+                                              const float* __restrict__ b1, const float* __restrict__ W2,
+                                              const float* __restrict__ b2, float* __restrict__ strong,
+                                              float* __restrict__ psoft, float* __restrict__ weak,
+                                              float* __restrict__ den, int T, uint32_t seed, uint32_t thr24,
+                                              float dscale, const unsigned* __restrict__ seed_dev,
+                                              const unsigned char* __restrict__ cvalid,
+                                              const unsigned char* __restrict__ pad) {
+    if (seed_dev) seed += *seed_dev;            // per-step entropy in device memory (hipGraph replays)
+    static_assert(NC <= 32, "the class mask of a frame is one 32-bit set");
+    constexpr int FPP = NTH / 4;                      // frames per pass
+    SED_DYN_SMEM(smem_w);                                      // (27 classes x 384 features x 2 matrices = 83 KB: above the static limit)
+    float* w1 = (float*)smem_w;                                // [NC][D]
+    float* w2 = w1 + NC * D;                                   // [NC][D]
+    __shared__ float red[NTH / 64][2 * NC];
+    const int tid = threadIdx.x, b = blockIdx.x, q = tid & 3;
+    for (int i = tid; i < NC * D; i += NTH) { w1[i] = W1[i]; w2[i] = W2[i]; }
+    __syncthreads();
+    float num[NC], dn[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) { num[c] = 0.f; dn[c] = 0.f; }
+    for (int t0 = 0; t0 < T; t0 += FPP) {                      // uniform trip count: the shuffles below need whole quads
+        const int t = t0 + (tid >> 2);
+        const bool live = t < T;
+        const float* xr = x + ((size_t)b * T + (live ? t : 0)) * D;
+        float l1[NC], l2[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) { l1[c] = 0.f; l2[c] = 0.f; }
+        if (live) {
+#pragma unroll 4
+            for (int i = 0; i < D / 16; ++i) {
+                const int k = 16 * i + 4 * q;
+                float4 v = *(const float4*)(xr + k);
+                const uint32_t e = (uint32_t)(((size_t)b * T + t) * D + k);
+                v.x = sed_keep(e, seed, thr24) ? v.x * dscale : 0.f;
+                v.y = sed_keep(e + 1, seed, thr24) ? v.y * dscale : 0.f;
+                v.z = sed_keep(e + 2, seed, thr24) ? v.z * dscale : 0.f;
+                v.w = sed_keep(e + 3, seed, thr24) ? v.w * dscale : 0.f;
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    const float4 a = *(const float4*)(w1 + c * D + k);
+                    const float4 g = *(const float4*)(w2 + c * D + k);
+                    l1[c] = fmaf(v.x, a.x, fmaf(v.y, a.y, fmaf(v.z, a.z, fmaf(v.w, a.w, l1[c]))));
+                    l2[c] = fmaf(v.x, g.x, fmaf(v.y, g.y, fmaf(v.z, g.z, fmaf(v.w, g.w, l2[c]))));
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            l1[c] = sed_quad_sum(l1[c]);
+            l2[c] = sed_quad_sum(l2[c]);
+        }
+        if (live && q == 0) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) { l1[c] += b1[c]; l2[c] += b2[c]; }
+            // CRNN.py:160-166: padded frames and the classes a clip's data set does not annotate cannot be attended to
+            // (masked_fill(-1e30) before the class softmax; a fully masked frame therefore attends uniformly)
+            // (the masks are gathered into one bit set first and applied with selects: the branchy form -- a conditional store
+            // per class behind `padded || (cvalid && !cvalid[...])` -- lost the fill in hipcc 7.2's code for gfx950)
+            unsigned inval = 0u;                                    // classes outside the clip's data set
+            if (cvalid) {
+#pragma unroll
+                for (int c = 0; c < NC; ++c) inval |= (cvalid[b * NC + c] ? 0u : 1u) << c;
+            }
+            const unsigned gone = (pad && pad[(size_t)b * T + t]) ? 0xFFFFFFFFu : inval;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) l2[c] = ((gone >> c) & 1u) ? -1e30f : l2[c];
+            float mx = l2[0];
+#pragma unroll
+            for (int c = 1; c < NC; ++c) mx = fmaxf(mx, l2[c]);
+            float se = 0.f;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) { l2[c] = expf(l2[c] - mx); se += l2[c]; }
+            const float inv = 1.0f / se;
+            float* so = strong + ((size_t)b * T + t) * NC;
+            float* po = psoft + ((size_t)b * T + t) * NC;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                const float s = sed_sigmoid(l1[c]);
+                const float p = l2[c] * inv;
+                const float a = fminf(fmaxf(p, 1e-7f), 1.0f);
+                so[c] = ((inval >> c) & 1u) ? 0.f : s;                    // CRNN.py:173-175 (after the pooling below)
+                po[c] = p;
+                num[c] += s * a;
+                dn[c] += a;
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const float a = wave_sum(num[c]), g = wave_sum(dn[c]);
+        if ((tid & 63) == 0) { red[tid >> 6][c] = a; red[tid >> 6][NC + c] = g; }
+    }
+    __syncthreads();
+    if (tid < NC) {
+        float n = 0.f, d = 0.f;
+#pragma unroll
+        for (int w = 0; w < NTH / 64; ++w) { n += red[w][tid]; d += red[w][NC + tid]; }
+        weak[b * NC + tid] = (cvalid && !cvalid[b * NC + tid]) ? 0.f : n / d;
+        den[b * NC + tid] = d;
+    }
+}
+template <int NC, int D>
+__global__ __launch_bounds__(HEAD_THREADS_WIDE) void head_fwd_wide_kernel(const float* __restrict__ x, const float* __restrict__ W1,
+                                                                          const float* __restrict__ b1, const float* __restrict__ W2,
+                                                                          const float* __restrict__ b2, float* __restrict__ strong,
+                                                                          float* __restrict__ psoft, float* __restrict__ weak,
+                                                                          float* __restrict__ den, int T, uint32_t seed, uint32_t thr24,
+                                                                          float dscale, const unsigned* __restrict__ seed_dev,
+                                                                          const unsigned char* __restrict__ cvalid,
+                                                                          const unsigned char* __restrict__ pad) {
+    head_fwd_body<NC, D, HEAD_THREADS_WIDE>(x, W1, b1, W2, b2, strong, psoft, weak, den, T, seed, thr24, dscale, seed_dev, cvalid, pad);
 }
 
 // backward: d_strong (B,T,NC), d_weak (B,NC) -> dx (B,T,D), dW1,dW2 (NC,D), db1,db2 (NC).  Every workgroup writes ONE partial record
@@ -300,13 +419,17 @@ SED_API int sed_head_fwd(const float* x, const float* W1, const float* b1, const
                             float* psoft, float* weak, float* den, int B, int T, int D, int NC, unsigned seed, unsigned thr24,
                             float dscale, const unsigned* seed_dev, const unsigned char* classes_valid, const unsigned char* pad_mask,
                             void* stream) {
-    if (D != 256 && D != 384) return SED_ERR_UNSUPPORTED;
+    if (D != 256 && D != 384 && D != 512) return SED_ERR_UNSUPPORTED;
     if (B <= 0 || T <= 0) return SED_OK;
     hipStream_t s = (hipStream_t)stream;
     const int smem_f = 2 * NC * D * 4;
 #define HEAD_CASE(nc, d) \
     if (NC == nc && D == d) { SED_MAX_SMEM((head_fwd_kernel<nc, d>), smem_f); SED_LAUNCH((head_fwd_kernel<nc, d>), dim3(B), dim3(HEAD_THREADS), smem_f, s, x, W1, b1, W2, b2, strong, psoft, weak, den, T, seed, thr24, dscale, seed_dev, classes_valid, pad_mask); return sed_check_launch(); }
     HEAD_CASE(10, 256) HEAD_CASE(27, 256) HEAD_CASE(10, 384) HEAD_CASE(27, 384)
+#undef HEAD_CASE
+#define HEAD_CASE(nc, d) \
+    if (NC == nc && D == d) { SED_MAX_SMEM((head_fwd_wide_kernel<nc, d>), smem_f); SED_LAUNCH((head_fwd_wide_kernel<nc, d>), dim3(B), dim3(HEAD_THREADS_WIDE), smem_f, s, x, W1, b1, W2, b2, strong, psoft, weak, den, T, seed, thr24, dscale, seed_dev, classes_valid, pad_mask); return sed_check_launch(); }
+    HEAD_CASE(10, 512) HEAD_CASE(27, 512)
 #undef HEAD_CASE
     return SED_ERR_UNSUPPORTED;
 }
@@ -316,7 +439,7 @@ SED_API int sed_head_bwd(const float* x, const float* W1, const float* W2, const
                             float* dW2, float* db1, float* db2, int B, int T, int D, int NC, unsigned seed, unsigned thr24,
                             float dscale, const unsigned* seed_dev, const unsigned char* classes_valid, const unsigned char* pad_mask,
                             float* scratch, void* stream) {
-    if (D != 256 && D != 384) return SED_ERR_UNSUPPORTED;
+    if (D != 256 && D != 384 && D != 512) return SED_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     const bool reduce = dW1 || dW2 || db1 || db2;          // all four null: records only, summed later by sed_head_bwd_reduce
     if (reduce && !(dW1 && dW2 && db1 && db2)) return SED_ERR_ARG;
@@ -327,7 +450,7 @@ SED_API int sed_head_bwd(const float* x, const float* W1, const float* W2, const
     int rc = SED_ERR_UNSUPPORTED;
 #define HEAD_CASE(nc, d) \
     if (NC == nc && D == d) { SED_MAX_SMEM((head_bwd_kernel<nc, d>), smem); SED_LAUNCH((head_bwd_kernel<nc, d>), dim3(gx, B), dim3(HEAD_BWD_THREADS(nc)), smem, s, x, W1, W2, strong, psoft, weak, den, d_strong, d_weak, dx, scratch, T, seed, thr24, dscale, seed_dev, classes_valid, pad_mask); rc = sed_check_launch(); }
-    HEAD_CASE(10, 256) HEAD_CASE(27, 256) HEAD_CASE(10, 384) HEAD_CASE(27, 384)
+    HEAD_CASE(10, 256) HEAD_CASE(27, 256) HEAD_CASE(10, 384) HEAD_CASE(27, 384) HEAD_CASE(10, 512) HEAD_CASE(27, 512)
 #undef HEAD_CASE
     if (rc != SED_OK || !reduce) return rc;
     SED_LAUNCH(head_bwd_reduce_kernel, dim3((NP + 63) / 64), dim3(256), 0, s, (const float*)scratch, gx * B, NP, NC * D, dW1, dW2, db1, db2, NC);
@@ -337,7 +460,7 @@ SED_API int sed_head_bwd(const float* x, const float* W1, const float* W2, const
 // pointers left in `scratch` (same B, T, D, NC).  Nothing on the backward chain reads them.
 SED_API int sed_head_bwd_reduce(const float* scratch, float* dW1, float* dW2, float* db1, float* db2, int B, int T, int D, int NC,
                                    void* stream) {
-    if (D != 256 && D != 384) return SED_ERR_UNSUPPORTED;
+    if (D != 256 && D != 384 && D != 512) return SED_ERR_UNSUPPORTED;
     if (!(dW1 && dW2 && db1 && db2)) return SED_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (B <= 0 || T <= 0) { sed_zero4(s, dW1, NC * D, dW2, NC * D, db1, NC, db2, NC); return SED_OK; }

@@ -13,6 +13,7 @@ dict, `forward(x, embeddings=emb (B, embedding_size, Te))`.
 Also built: `aggregation_type="interpolate"` (nearest-exact, CRNN.py:271-279, the same fused kernel), `dropstep_recurrent`
 (CRNN.py:288-301: per-clip time spans of the recurrent stage's input zeroed, independently for the CNN features and the
 embeddings), `classes_mask` / `pad_mask` of the multi-data-set recipes (CRNN.py:157-176) inside the head kernels.
+`n_RNN_cell` is 128 (2023 recipe), 192 (2024 recipe) or 256 (the third value of the 2024 recipe's search; opt-in: SED_GRU_WIDE=1 or ops.GRU_WIDE = True); other widths raise.
 
 Not built (they raise NotImplementedError): aggregation_type "frame" (a 512-unit BiGRU encoder over the embedding frames, used by
 no recipe configuration) and "global" (in the reference itself this branch ends in an undefined `reshape_emb`, CRNN.py:249-262 +

@@ -1,15 +1,21 @@
 """Bidirectional GRU container (state-dict layout of desed_task/nnet/RNN.py:7-30: `rnn.weight_ih_l{k}[_reverse]` ...).
-nn.GRU is used as the parameter holder / initialiser only; the arithmetic is ops.BiGRULayerFn."""
+nn.GRU is used as the parameter holder / initialiser only; the arithmetic is ops.BiGRULayerFn.
+n_hidden: 128 (2023 recipe), 192 (2024 recipe) or 256 (the widest n_RNN_cell of the 2024 recipe's search; opt-in, ops.GRU_WIDE / SED_GRU_WIDE=1); other widths raise."""
 import torch.nn as nn
 
+from .. import ops as _ops
 from ..ops import BiGRULayerFn
 
 
 class BidirectionalGRU(nn.Module):
     def __init__(self, n_in, n_hidden, dropout=0, num_layers=1):
         super().__init__()
-        if n_hidden not in (128, 192):
-            raise NotImplementedError("HIP GRU kernels are built for n_hidden = 128 and 192 (the 2023 / 2024 recipes' n_RNN_cell)")
+        if n_hidden == 256 and not _ops.GRU_WIDE:
+            raise NotImplementedError("n_hidden = 256 runs on the streamed-weight GRU kernels and is opt-in: set SED_GRU_WIDE=1 (or "
+                                      "desed_task_amd.ops.GRU_WIDE = True) before building the model; 128 and 192 need no switch")
+        if n_hidden not in (128, 192, 256):
+            raise NotImplementedError("HIP GRU kernels are built for n_hidden = 128, 192 and 256 (the 2023 / 2024 recipes' n_RNN_cell "
+                                      "and the widest value of the 2024 recipe's search), not %d" % n_hidden)
         if dropout:
             raise NotImplementedError("inter-layer GRU dropout (dropout_recurrent) is not on the 2023 path")
         self.num_layers = num_layers

@@ -24,6 +24,10 @@ GRU_DW_ATOMIC = False            # A/B switch (bench.py --gru-dw-atomic): the ze
 # the other layer's recurrence (96 workgroups: 160 CUs idle).  Only launcher.StepDriver.backward_joined() turns it on, for the
 # duration of its loss.backward(), and joins the side stream before returning (same-box step 4.17 -> 4.13 ms).
 GRU_DW_SIDE = False
+# n_RNN_cell = 256 (the third value of the 2024 recipe's search) is opt-in: SED_GRU_WIDE=1, or ops.GRU_WIDE = True before the model is
+# built.  Off, nnet.RNN refuses the width as it always has; the kernels behind it (csrc/sed_gru.hip: W_hh streamed from L2) are in the
+# library either way.  DESIGN.md, "Recurrence at n_RNN_cell = 256".
+GRU_WIDE = os.environ.get("SED_GRU_WIDE", "0") == "1"
 GRU_DX_SPLITK = True             # bench.py --no-dx-splitk (A/B): the BiGRU dX product as one K slice
 GRU_DW_SIDE_ALLOWED = True       # bench.py --no-gru-dw-side (A/B)
 # Round 5: the weight-gradient GEMMs of CNN blocks 1-6 take the same way out (they were ~390 us of a backward chain that ran one kernel
@@ -475,7 +479,7 @@ def _gemm(lib, A, Bm, bias, C, M, N, K, lda, ldb, ldc, ta, tb, split_k, accumula
 
 
 class BiGRULayerFn(torch.autograd.Function):
-    """One bidirectional GRU layer (nn.GRU semantics, RNN.py:19-30).  x (B,T,I) -> (B,T,2H), H = 128.
+    """One bidirectional GRU layer (nn.GRU semantics, RNN.py:19-30).  x (B,T,I) -> (B,T,2H), H = 128, 192 or 256.
     Input projections and all weight gradients are MFMA GEMMs; the recurrence is the persistent kernel."""
 
     @staticmethod
@@ -699,7 +703,7 @@ class DropStepFn(torch.autograd.Function):
 
 class HeadFn(torch.autograd.Function):
     """Dropout + the two dense layers + class-softmax attention pooling (CRNN.py:152-178, :304).
-    x (B,T,256) -> strong (B,T,NC) [caller exposes the (B,NC,T) view], weak (B,NC)."""
+    x (B,T,D), D = 2 H = 256, 384 or 512 -> strong (B,T,NC) [caller exposes the (B,NC,T) view], weak (B,NC)."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, cfg):

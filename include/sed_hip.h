@@ -251,7 +251,8 @@ int sed_colsum(const float* X, float* out, float* out1, int nsplit, int M, int N
 
 /* GRU recurrence of one layer, both directions: gi (B,T,2,3H) = W_ih x + b_ih per direction; whh0/whh1 (3H,H),
  * bhh0/bhh1 (3H) = forward / reverse direction; out (B,T,2H); saved (B,T,2,4,H) = r,z,n,hn or null.
- * H = 128 (2023 recipe) or 192 (2024 recipe's n_RNN_cell); other widths return SED_ERR_UNSUPPORTED. */
+ * H = 128 (2023 recipe), 192 (2024 recipe's n_RNN_cell) or 256 (the widest value of the 2024 recipe's search; part of W_hh is
+ * re-read from L2 every step, DESIGN.md "Recurrence at n_RNN_cell = 256"); other widths return SED_ERR_UNSUPPORTED. */
 int sed_gru_fwd(const float* gi, const float* whh0, const float* whh1, const float* bhh0, const float* bhh1,
                 float* out, float* saved, int B, int T, int H, void* stream);
 
@@ -269,7 +270,7 @@ int sed_gru_bias_reduce(const float* scratch, float* dbi0, float* dbi1, float* d
 
 /* ---- K8 + K9: attention-pooling head (desed_task/nnet/CRNN.py:152-178, dropout :304) and losses ---------------- */
 
-/* x (B,T,D), D = 256 or 384 (= 2 * n_RNN_cell), NC = 10 or 27 -> strong (B,T,NC) = sigmoid(dense), psoft (B,T,NC) = softmax over classes of dense_softmax,
+/* x (B,T,D), D = 256, 384 or 512 (= 2 * n_RNN_cell), NC = 10 or 27 -> strong (B,T,NC) = sigmoid(dense), psoft (B,T,NC) = softmax over classes of dense_softmax,
  * weak (B,NC) = sum_t(strong*clamp(psoft)) / sum_t(clamp(psoft)), den (B,NC) = the denominators.
  * classes_valid (B,NC) bytes or null: the `classes_mask` of the multi-data-set recipes (CRNN.py:157-176; non-zero = the clip's
  * data set annotates the class): other classes cannot be attended to and their strong / weak outputs are 0.  pad_mask (B,T)

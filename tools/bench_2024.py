@@ -2,7 +2,8 @@
 `recipes/dcase2024_task4_baseline/confs/pretrained.yaml` -- batch [12, 6, 6, 12, 24] = 60 clips of 10 s, 27 classes, n_RNN_cell 192,
 dropout 0.5, dropstep_recurrent 0.3 x 16, frozen 768 x 496 embeddings per clip, mixup on features and embeddings, class masks --
 random weights, synthetic data.  Secondary workload: not the headline metric of bench.py.
-    python tools/bench_2024.py [--graph] [--prefetch] [--gradient-clip X]
+    python tools/bench_2024.py [--graph] [--prefetch] [--gradient-clip X] [--n-rnn-cell H]
+--n-rnn-cell H: `net.n_RNN_cell` (default 192, the recipe's; its hyper-parameter search also draws 128 and 256; 256 switches ops.GRU_WIDE on).
 --gradient-clip X: `training.gradient_clip` (confs/pretrained.yaml:17 ships 5.0) -- norm clipping inside the fused optimizer step; the
 JSON line then carries the last step's {norm, coef} (arena.FusedAdam.last_clip)."""
 import json, os, random, sys, time
@@ -17,11 +18,15 @@ from desed_task_amd.utils.schedulers import ExponentialWarmup
 from bench import recipe_config
 
 BS, NCLASS = (12, 6, 6, 12, 24), 27
+N_RNN_CELL = int(sys.argv[sys.argv.index("--n-rnn-cell") + 1]) if "--n-rnn-cell" in sys.argv else 192
+if N_RNN_CELL == 256:
+    from desed_task_amd import ops as _ops_
+    _ops_.GRU_WIDE = True
 dev = torch.device("cuda", 0)
 torch.manual_seed(1); np.random.seed(1); random.seed(1)
 config = recipe_config()
 config["training"].update(batch_size=list(BS), mixup="soft", mixup_prob=0.5, epoch_decay=100, const_max=2)
-config["net"].update(dropout=0.5, rnn_layers=1, nclass=NCLASS, n_RNN_cell=192, dropstep_recurrent=0.3, dropstep_recurrent_len=16,
+config["net"].update(dropout=0.5, rnn_layers=1, nclass=NCLASS, n_RNN_cell=N_RNN_CELL, dropstep_recurrent=0.3, dropstep_recurrent_len=16,
                      use_embeddings=True, embedding_size=768, embedding_type="frame", aggregation_type="pool1d")
 config["pretrained"] = {"e2e": False, "freezed": True, "model": "beats"}
 if "--gradient-clip" in sys.argv:
@@ -81,7 +86,7 @@ for i in range(K):
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / K
 # per-entry roofline rows like bench.py's: HIP events around every launch of 3 eager steps after the timed region
-# (the 2024 step's entries are the CRNN step's + sed_embcat: bench.py's work table applies; shapes with n_RNN_cell = 192)
+# (the 2024 step's entries are the CRNN step's + sed_embcat: bench.py's work table applies; shapes with n_RNN_cell = 192 by default)
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import KernelTimer, roofline_tables, PEAK_BF16_MFMA_TFLOPS
 from desed_task_amd import _lib as _lib_
@@ -104,8 +109,8 @@ torch.cuda.synchronize()
 timer.unwrap()
 rows, families = roofline_tables(timer.summary(), EAGER, dt * 1e3, task.sed_student.cnn.conv_precision)
 clips_s = B / dt
-print(json.dumps({"workload": "dcase2024 pretrained.yaml training step: batch 60 = [12,6,6,12,24] x 10 s, 27 classes, n_RNN_cell 192, "
-                              "768 x 496 embeddings per clip, dropout + dropstep + mixup on", "launch": "hipGraph" if "--graph" in sys.argv else "eager",
+print(json.dumps({"workload": "dcase2024 pretrained.yaml training step: batch 60 = [12,6,6,12,24] x 10 s, 27 classes, n_RNN_cell %d, "
+                              "768 x 496 embeddings per clip, dropout + dropstep + mixup on" % N_RNN_CELL, "launch": "hipGraph" if "--graph" in sys.argv else "eager",
                   "front_end": "pipelined (teacher)" if pipelined else "inline",
                   "gradient_clip": config["training"].get("gradient_clip"),
                   "last_clip": [float(x) for x in opt.last_clip.cpu()] if opt.last_clip is not None else None,

@@ -1,4 +1,4 @@
-"""Times one BiGRU layer (forward and backward through ops.BiGRULayerFn) at B = 48, T = 156 for the two recurrent widths (diagnostics)."""
+"""Times one BiGRU layer (forward and backward through ops.BiGRULayerFn) at B = 48, T = 156 for the three recurrent widths (diagnostics)."""
 import sys
 import torch
 sys.path.insert(0, ".")
@@ -8,7 +8,7 @@ if len(sys.argv) > 1:                 # A/B: another build of the C-ABI library 
     _lib.use_library(sys.argv[1], is_emulator=False)
 lib = _lib.get(); orig = lib.call
 B, T = 48, 156
-for H, I in ((128, 128), (128, 256), (192, 128), (192, 384)):
+for H, I in ((128, 128), (128, 256), (192, 128), (192, 384), (256, 128), (256, 512)):
     x = torch.randn(B, T, I, device="cuda", requires_grad=True)
     ws = []
     for _ in range(2):
