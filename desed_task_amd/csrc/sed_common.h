@@ -226,6 +226,23 @@ __device__ __forceinline__ void bf16_split2(float a, float b, unsigned& hi, unsi
     lo = __builtin_bit_cast(unsigned, __builtin_convertvector(v - hf, bf16x2_t));
 #endif
 }
+// Product count of a contraction kernel, from a trailing pack of marker types: none = 3 (the split-bf16 kernels keep the names they always
+// had -- an empty pack leaves the DEMANGLED name as it was (the mangled symbol gains an empty `JE`); profiles, tools/isa_exposed_loads.py and tests/test_isa_audit.py know the
+// kernels by name -- and the instructions they always had), <..., SedOneProduct> = the single-product twin.
+struct SedOneProduct {};
+template <class... ONE>
+constexpr int sed_np() { return sizeof...(ONE) ? 1 : 3; }
+// The hi half alone (the single-product "bf16" mode: both operands rounded once, no lo plane): the same v_cvt_pk_bf16_f32.
+__device__ __forceinline__ unsigned bf16_round2(float a, float b) {
+#ifdef SED_EMU
+    return (unsigned)f32_to_bf16(a) | ((unsigned)f32_to_bf16(b) << 16);
+#else
+    typedef float f32x2_t __attribute__((ext_vector_type(2)));
+    typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+    const f32x2_t v = {a, b};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
+#endif
+}
 
 __device__ __forceinline__ f32x16 f32x16_zero() {
     f32x16 z;

@@ -646,27 +646,36 @@ static int launch_wgrad(const float* x, const float* dy, float* dWp, int B, int 
 // was 0.50 with the earlier 72-element pitch and row >> 4 swizzle).  The tap shift is applied when the x block is fetched, so
 // every LDS access is aligned.  The next K tile is fetched into registers under the MFMAs.
 // ---------------------------------------------------------------------------------------------
-template <int CIN, int COUT>
+// NP = 3: three MFMAs per product on hi / lo planes.  NP = 1 (the "bf16" mode, sed_conv_wgrad_bf16x1): x and dy rounded once, one MFMA per
+// product, no lo planes (PLANES = 1: half the LDS, half the transposing stores and fragment reads); same tiles, same pixel order.
+template <int CIN, int COUT, int NP = 3>
 struct WgbCfg {
+    static constexpr int PLANES = NP == 1 ? 1 : 2;
     static constexpr int KT = 64, RS = 64;              // pixels per K tile, LDS row stride (bf16)
     static constexpr int MT = CIN / 32, NT = COUT / 32;
     static constexpr int WM = MT >= 4 ? 2 : 1, WN = 4 / WM;
     static constexpr int MTW = MT / WM, NTW = NT / WN;
     static constexpr int NBX = (KT / 4) * (CIN / 4) / 256, NBD = (KT / 4) * (COUT / 4) / 256;   // 4x4 blocks per thread
-    static constexpr int SMEM = 2 * (CIN + COUT) * RS * 2;
+    static constexpr int SMEM = PLANES * (CIN + COUT) * RS * 2;
     static_assert(NBX >= 1 && NBD >= 1 && MTW * WM == MT && NTW * WN == NT, "tile split");
 };
 
 // 4 pixels x 4 channels (vj = pixel j) -> rows 4cq..4cq+3 of the [channel][pixel] hi / lo planes, pixels 4pq..4pq+3.
 // (Plain scalars only: pointer / reference arrays over the register blocks would push them to scratch.)
+template <bool LO = true>
 __device__ __forceinline__ void wgb_store_row(float a, float b, float c, float d, unsigned short* __restrict__ hi_row,
                                               unsigned short* __restrict__ lo_row) {
+    if constexpr (!LO) {
+        *(uint2*)hi_row = make_uint2(bf16_round2(a, b), bf16_round2(c, d));
+    } else {
     uint2 h, l;
     bf16_split2(a, b, h.x, l.x);
     bf16_split2(c, d, h.y, l.y);
     *(uint2*)hi_row = h;
     *(uint2*)lo_row = l;
+    }
 }
+template <bool LO = true>
 __device__ __forceinline__ void wgb_store_block(const float4 v0, const float4 v1, const float4 v2, const float4 v3,
                                                 unsigned short* __restrict__ hi_plane, unsigned short* __restrict__ lo_plane,
                                                 int cq, int pq, int RS) {
@@ -674,22 +683,23 @@ __device__ __forceinline__ void wgb_store_block(const float4 v0, const float4 v1
     const int r0 = 4 * cq, f0 = (r0 ^ cq) & 7;
     const int o0 = r0 * RS + 4 * (pq ^ (2 * f0)), o1 = (r0 + 1) * RS + 4 * (pq ^ (2 * (f0 ^ 1)));
     const int o2 = (r0 + 2) * RS + 4 * (pq ^ (2 * (f0 ^ 2))), o3 = (r0 + 3) * RS + 4 * (pq ^ (2 * (f0 ^ 3)));
-    wgb_store_row(v0.x, v1.x, v2.x, v3.x, hi_plane + o0, lo_plane + o0);
-    wgb_store_row(v0.y, v1.y, v2.y, v3.y, hi_plane + o1, lo_plane + o1);
-    wgb_store_row(v0.z, v1.z, v2.z, v3.z, hi_plane + o2, lo_plane + o2);
-    wgb_store_row(v0.w, v1.w, v2.w, v3.w, hi_plane + o3, lo_plane + o3);
+    wgb_store_row<LO>(v0.x, v1.x, v2.x, v3.x, hi_plane + o0, lo_plane + o0);
+    wgb_store_row<LO>(v0.y, v1.y, v2.y, v3.y, hi_plane + o1, lo_plane + o1);
+    wgb_store_row<LO>(v0.z, v1.z, v2.z, v3.z, hi_plane + o2, lo_plane + o2);
+    wgb_store_row<LO>(v0.w, v1.w, v2.w, v3.w, hi_plane + o3, lo_plane + o3);
 }
 
-template <int CIN, int COUT>
+template <int CIN, int COUT, class... ONE>
 __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                               float* __restrict__ dWp, int B, int T, int F) {
-    using Cfg = WgbCfg<CIN, COUT>;
+    constexpr int NP = sed_np<ONE...>();
+    using Cfg = WgbCfg<CIN, COUT, NP>;
     constexpr int KT = Cfg::KT, RS = Cfg::RS, WN = Cfg::WN, MTW = Cfg::MTW, NTW = Cfg::NTW, NBX = Cfg::NBX, NBD = Cfg::NBD;
     SED_DYN_SMEM(smem);
     unsigned short* xh = (unsigned short*)smem;      // [CIN][RS] hi, then lo
-    unsigned short* xl = xh + CIN * RS;
+    unsigned short* xl = xh + (Cfg::PLANES - 1) * CIN * RS;      // (NP = 1: no lo planes -- never written, never read)
     unsigned short* dh = xl + CIN * RS;              // [COUT][RS] hi, then lo
-    unsigned short* dl = dh + COUT * RS;
+    unsigned short* dl = dh + (Cfg::PLANES - 1) * COUT * RS;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lo = lane & 31, hi = lane >> 5;
     const int wn = w % WN, wm = w / WN;
     const int tap = blockIdx.y, da = tap / 3 - 1, db = tap % 3 - 1;
@@ -745,13 +755,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const float* __res
 #pragma unroll
         for (int u = 0; u < NBX; ++u) {
             const int blk = tid + 256 * u;
-            wgb_store_block(rx[4 * u], rx[4 * u + 1], rx[4 * u + 2], rx[4 * u + 3], xh, xl, (blk >> 1) % (CIN / 4),
+            wgb_store_block<NP != 1>(rx[4 * u], rx[4 * u + 1], rx[4 * u + 2], rx[4 * u + 3], xh, xl, (blk >> 1) % (CIN / 4),
                             (blk & 1) + 2 * ((blk >> 1) / (CIN / 4)), RS);
         }
 #pragma unroll
         for (int u = 0; u < NBD; ++u) {
             const int blk = tid + 256 * u;
-            wgb_store_block(rd[4 * u], rd[4 * u + 1], rd[4 * u + 2], rd[4 * u + 3], dh, dl, (blk >> 1) % (COUT / 4),
+            wgb_store_block<NP != 1>(rd[4 * u], rd[4 * u + 1], rd[4 * u + 2], rd[4 * u + 3], dh, dl, (blk >> 1) % (COUT / 4),
                             (blk & 1) + 2 * ((blk >> 1) / (COUT / 4)), RS);
         }
     };
@@ -772,13 +782,18 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const float* __res
                 const int row = (wm * MTW + m) * 32 + lo;
                 const int off = row * RS + 8 * (oct ^ ((row ^ (row >> 2)) & 7));
                 a_hi[m] = *(const s16x8*)(xh + off);
-                a_lo[m] = *(const s16x8*)(xl + off);
+                if constexpr (NP != 1) a_lo[m] = *(const s16x8*)(xl + off);
             }
 #pragma unroll
             for (int n = 0; n < NTW; ++n) {
                 const int row = (wn * NTW + n) * 32 + lo;
                 const int off = row * RS + 8 * (oct ^ ((row ^ (row >> 2)) & 7));
                 const s16x8 b_hi = *(const s16x8*)(dh + off);
+                if constexpr (NP == 1) {
+#pragma unroll
+                    for (int m = 0; m < MTW; ++m) acc[m][n] = mfma32_bf16(a_hi[m], b_hi, acc[m][n]);
+                    continue;
+                }
                 const s16x8 b_lo = *(const s16x8*)(dl + off);
 #pragma unroll
                 for (int m = 0; m < MTW; ++m) {
@@ -801,12 +816,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_kernel(const float* __res
         }
 }
 
-template <int CIN, int COUT>
+template <int CIN, int COUT, int NP = 3>
 static int launch_wgrad_bf16(const float* x, const float* dy, float* dWp, int B, int T, int F, hipStream_t s) {
-    using Cfg = WgbCfg<CIN, COUT>;
+    using Cfg = WgbCfg<CIN, COUT, NP>;
     const int splits = wgrad_parts(CIN, COUT, B, T, F);
-    SED_MAX_SMEM((conv_wgrad_bf16_kernel<CIN, COUT>), Cfg::SMEM);
-    SED_LAUNCH((conv_wgrad_bf16_kernel<CIN, COUT>), dim3(splits, 9), dim3(256), Cfg::SMEM, s, x, dy, dWp, B, T, F);
+    SED_MAX_SMEM((NP == 1 ? conv_wgrad_bf16_kernel<CIN, COUT, SedOneProduct> : conv_wgrad_bf16_kernel<CIN, COUT>), Cfg::SMEM);
+    SED_LAUNCH((NP == 1 ? conv_wgrad_bf16_kernel<CIN, COUT, SedOneProduct> : conv_wgrad_bf16_kernel<CIN, COUT>), dim3(splits, 9), dim3(256), Cfg::SMEM, s, x, dy, dWp, B, T, F);
     return sed_check_launch();
 }
 
@@ -821,26 +836,28 @@ static int launch_wgrad_bf16(const float* x, const float* dy, float* dWp, int B,
 // stay at 96 VGPRs because a workgroup owns COH = 64 of the 128 output channels when CIN = 128 (grid z = 2).  Traffic: x is read
 // 3 x (COUT / COH) times, dy 3 times, instead of 9 + 9.
 // ---------------------------------------------------------------------------------------------
-template <int CIN, int COUT, int COH>
+template <int CIN, int COUT, int COH, int NP = 3>
 struct WgrCfg {
+    static constexpr int PLANES = NP == 1 ? 1 : 2;
     static constexpr int KT = 64, RS = 64;
     static constexpr int MT = CIN / 32, NT = COH / 32;
     static constexpr int WM = MT >= 4 ? 2 : 1, WN = 4 / WM;
     static constexpr int MTW = MT / WM, NTW = NT / WN;
     static constexpr int NBX = (KT / 4) * (CIN / 4) / 256, NBD = (KT / 4) * (COH / 4) / 256;
-    static constexpr int SMEM = 2 * (CIN + COH) * RS * 2;
+    static constexpr int SMEM = PLANES * (CIN + COH) * RS * 2;
     static_assert(NBX >= 1 && NBD >= 1 && MTW * WM == MT && NTW * WN == NT && MTW * NTW == 2, "tile split");
 };
-template <int CIN, int COUT, int COH>
+template <int CIN, int COUT, int COH, class... ONE>
 __global__ __launch_bounds__(256) void conv_wgrad_bf16_row_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                                   float* __restrict__ dWp, int B, int T, int F) {
-    using Cfg = WgrCfg<CIN, COUT, COH>;
+    constexpr int NP = sed_np<ONE...>();
+    using Cfg = WgrCfg<CIN, COUT, COH, NP>;
     constexpr int KT = Cfg::KT, RS = Cfg::RS, WN = Cfg::WN, MTW = Cfg::MTW, NTW = Cfg::NTW, NBX = Cfg::NBX, NBD = Cfg::NBD;
     SED_DYN_SMEM(smem);
     unsigned short* xh = (unsigned short*)smem;      // [CIN][RS] hi, then lo
-    unsigned short* xl = xh + CIN * RS;
+    unsigned short* xl = xh + (Cfg::PLANES - 1) * CIN * RS;      // (NP = 1: no lo planes -- never written, never read)
     unsigned short* dh = xl + CIN * RS;              // [COH][RS] hi, then lo
-    unsigned short* dl = dh + COH * RS;
+    unsigned short* dl = dh + (Cfg::PLANES - 1) * COH * RS;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int tid = threadIdx.x, lo = lane & 31, hi = lane >> 5;
     const int wn = w % WN, wm = w / WN;
@@ -902,13 +919,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_row_kernel(const float* _
 #pragma unroll
         for (int u = 0; u < NBX; ++u) {
             const int blk = tid + 256 * u;
-            wgb_store_block(rx[4 * u], rx[4 * u + 1], rx[4 * u + 2], rx[4 * u + 3], xh, xl, (blk >> 1) % (CIN / 4),
+            wgb_store_block<NP != 1>(rx[4 * u], rx[4 * u + 1], rx[4 * u + 2], rx[4 * u + 3], xh, xl, (blk >> 1) % (CIN / 4),
                             (blk & 1) + 2 * ((blk >> 1) / (CIN / 4)), RS);
         }
 #pragma unroll
         for (int u = 0; u < NBD; ++u) {
             const int blk = tid + 256 * u;
-            wgb_store_block(rd[4 * u], rd[4 * u + 1], rd[4 * u + 2], rd[4 * u + 3], dh, dl, (blk >> 1) % (COH / 4),
+            wgb_store_block<NP != 1>(rd[4 * u], rd[4 * u + 1], rd[4 * u + 2], rd[4 * u + 3], dh, dl, (blk >> 1) % (COH / 4),
                             (blk & 1) + 2 * ((blk >> 1) / (COH / 4)), RS);
         }
     };
@@ -942,6 +959,14 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_row_kernel(const float* _
                 const int row = (wm * MTW + m) * 32 + lo, sw = (row ^ (row >> 2)) & 7;
                 const int off = row * RS + 8 * (oct ^ sw);
                 const int offp = row * RS + 8 * (((oct + 7) & 7) ^ sw) + 6, offn = row * RS + 8 * (((oct + 1) & 7) ^ sw);
+                if constexpr (NP == 1) {
+                    const uint4 ch = *(const uint4*)(xh + off);
+                    const unsigned ph = first ? 0u : *(const unsigned*)(xh + offp), nh = last ? 0u : *(const unsigned*)(xh + offn);
+                    a_hi[0][m] = __builtin_bit_cast(s16x8, shift_m1(ch, ph));
+                    a_hi[1][m] = __builtin_bit_cast(s16x8, ch);
+                    a_hi[2][m] = __builtin_bit_cast(s16x8, shift_p1(ch, nh));
+                    continue;
+                }
                 const uint4 ch = *(const uint4*)(xh + off), cl = *(const uint4*)(xl + off);
                 const unsigned ph = first ? 0u : *(const unsigned*)(xh + offp), pl = first ? 0u : *(const unsigned*)(xl + offp);
                 const unsigned nh = last ? 0u : *(const unsigned*)(xh + offn), nl = last ? 0u : *(const unsigned*)(xl + offn);
@@ -954,6 +979,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_row_kernel(const float* _
                 const int row = (wn * NTW + n) * 32 + lo;
                 const int off = row * RS + 8 * (oct ^ ((row ^ (row >> 2)) & 7));
                 const s16x8 b_hi = *(const s16x8*)(dh + off);
+                if constexpr (NP == 1) {
+#pragma unroll
+                    for (int t3 = 0; t3 < 3; ++t3)
+#pragma unroll
+                        for (int m = 0; m < MTW; ++m) acc[t3][m][n] = mfma32_bf16(a_hi[t3][m], b_hi, acc[t3][m][n]);
+                    continue;
+                }
                 const s16x8 b_lo = *(const s16x8*)(dl + off);
 #pragma unroll
                 for (int t3 = 0; t3 < 3; ++t3)
@@ -980,11 +1012,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_bf16_row_kernel(const float* _
             }
     }
 }
-template <int CIN, int COUT, int COH>
+template <int CIN, int COUT, int COH, int NP = 3>
 static int launch_wgrad_bf16_row(const float* x, const float* dy, float* dWp, int B, int T, int F, int splits, hipStream_t s) {
-    using Cfg = WgrCfg<CIN, COUT, COH>;
-    SED_MAX_SMEM((conv_wgrad_bf16_row_kernel<CIN, COUT, COH>), Cfg::SMEM);
-    SED_LAUNCH((conv_wgrad_bf16_row_kernel<CIN, COUT, COH>), dim3(splits, 3, COUT / COH), dim3(256), Cfg::SMEM, s, x, dy, dWp, B, T, F);
+    using Cfg = WgrCfg<CIN, COUT, COH, NP>;
+    SED_MAX_SMEM((NP == 1 ? conv_wgrad_bf16_row_kernel<CIN, COUT, COH, SedOneProduct> : conv_wgrad_bf16_row_kernel<CIN, COUT, COH>), Cfg::SMEM);
+    SED_LAUNCH((NP == 1 ? conv_wgrad_bf16_row_kernel<CIN, COUT, COH, SedOneProduct> : conv_wgrad_bf16_row_kernel<CIN, COUT, COH>), dim3(splits, 3, COUT / COH), dim3(256), Cfg::SMEM, s, x, dy, dWp, B, T, F);
     return sed_check_launch();
 }
 
@@ -1183,25 +1215,28 @@ static int launch_wgrad_alltaps(const float* x, const float* dy, float* dWp, int
 #ifndef WGN_ABL
 #define WGN_ABL 0
 #endif
-template <int CIN, int COUT>
+template <int CIN, int COUT, int NP = 3>
 struct WgnCfg {
+    static constexpr int PLANES = NP == 1 ? 1 : 2;       // (NP = 1, the "bf16" mode: no lo planes, as in WgbCfg)
     static constexpr int TF = 32, TR = 4, PH = TR + 2;
     static constexpr bool M16 = CIN == 16;
     static constexpr int XS = PH * TF + (M16 ? 16 : 8), DS = TR * TF + (M16 ? 16 : 8);     // channel pitch (bf16 elements)
     static constexpr int XPLANE = CIN * XS, DPLANE = COUT * DS;
-    static constexpr int SMEM_OPS = (6 * XPLANE + 2 * DPLANE) * 2, SMEM_RED = 9 * CIN * COUT * 4;
+    static constexpr int SMEM_OPS = (3 * PLANES * XPLANE + PLANES * DPLANE) * 2, SMEM_RED = 9 * CIN * COUT * 4;
     static constexpr int SMEM = SMEM_OPS > SMEM_RED ? SMEM_OPS : SMEM_RED;
 };
-template <int CIN, int COUT>
+template <int CIN, int COUT, class... ONE>
 __global__ __launch_bounds__(256) void conv_wgrad_alltaps_bf16_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                                       float* __restrict__ dWp, int B, int T, int F) {
-    using Cfg = WgnCfg<CIN, COUT>;
+    constexpr int NP = sed_np<ONE...>();
+    using Cfg = WgnCfg<CIN, COUT, NP>;
+    constexpr int PLANES = Cfg::PLANES;
     constexpr int TF = Cfg::TF, TR = Cfg::TR, PH = Cfg::PH, XS = Cfg::XS, DS = Cfg::DS, XPLANE = Cfg::XPLANE, DPLANE = Cfg::DPLANE;
     constexpr bool M16 = Cfg::M16;
     static_assert((CIN == 16 && COUT == 32) || (CIN == 32 && COUT == 64), "the two narrow layers of the recipe");
     SED_DYN_SMEM(smem);
     unsigned short* xp = (unsigned short*)smem;          // [column shift 3][hi | lo][CIN][XS]: x[t0 - 1 + i][f0 + c + shift - 1]
-    unsigned short* dp = xp + 6 * XPLANE;                // [hi | lo][COUT][DS]:                dy[t0 + r][f0 + c]
+    unsigned short* dp = xp + 3 * PLANES * XPLANE;                // [hi | lo][COUT][DS]:                dy[t0 + r][f0 + c]
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     int tid = threadIdx.x, lo = lane & 31, hi = lane >> 5, i16 = lane & 15, g = lane >> 4;
     const int ftiles = F / TF, ttiles = (T + TR - 1) / TR, ntiles = B * ttiles * ftiles;
@@ -1276,15 +1311,18 @@ __global__ __launch_bounds__(256) void conv_wgrad_alltaps_bf16_kernel(const floa
                     // the five neighbouring pixel pairs of this channel, split once; shift s uses pairs (s, s + 2)
                     unsigned ph[5], pl[5];
 #pragma unroll
-                    for (int k = 0; k < 5; ++k) bf16_split2(comp(lx[u][k], c), comp(lx[u][k + 1], c), ph[k], pl[k]);
+                    for (int k = 0; k < 5; ++k) {
+                        if constexpr (NP == 1) ph[k] = bf16_round2(comp(lx[u][k], c), comp(lx[u][k + 1], c));
+                        else bf16_split2(comp(lx[u][k], c), comp(lx[u][k + 1], c), ph[k], pl[k]);
+                    }
                     unsigned short* dst = xp + (4 * v + c) * XS + i * TF + 4 * cq;
 #pragma unroll
                     for (int sft = 0; sft < 3; ++sft) {
                         uint2 hv, lv;
                         hv.x = ph[sft]; hv.y = ph[sft + 2];
-                        lv.x = pl[sft]; lv.y = pl[sft + 2];
-                        *(uint2*)(dst + (2 * sft) * XPLANE) = hv;
-                        *(uint2*)(dst + (2 * sft + 1) * XPLANE) = lv;
+                        if constexpr (NP != 1) { lv.x = pl[sft]; lv.y = pl[sft + 2]; }
+                        *(uint2*)(dst + (PLANES * sft) * XPLANE) = hv;
+                        if constexpr (NP != 1) *(uint2*)(dst + (2 * sft + 1) * XPLANE) = lv;
                     }
                 }
             }
@@ -1294,6 +1332,11 @@ __global__ __launch_bounds__(256) void conv_wgrad_alltaps_bf16_kernel(const floa
             const int it = tid + 256 * u, cq = it % 8, v = (it / 8) % VD, r = it / (8 * VD);
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
+                if constexpr (NP == 1) {
+                    *(uint2*)(dp + (4 * v + c) * DS + r * TF + 4 * cq) =
+                        make_uint2(bf16_round2(comp(ld[u][0], c), comp(ld[u][1], c)), bf16_round2(comp(ld[u][2], c), comp(ld[u][3], c)));
+                    continue;
+                }
                 uint2 hv, lv;
                 bf16_split2(comp(ld[u][0], c), comp(ld[u][1], c), hv.x, lv.x);
                 bf16_split2(comp(ld[u][2], c), comp(ld[u][3], c), hv.y, lv.y);
@@ -1321,13 +1364,13 @@ __global__ __launch_bounds__(256) void conv_wgrad_alltaps_bf16_kernel(const floa
             for (int nt = 0; nt < 2; ++nt) {
                 const unsigned short* bp = dp + (16 * nt + i16) * DS + w * TF + 8 * g;
                 bh[nt] = *(const s16x8*)bp;
-                bl[nt] = *(const s16x8*)(bp + DPLANE);
+                if constexpr (NP != 1) bl[nt] = *(const s16x8*)(bp + DPLANE);
             }
 #pragma unroll
             for (int tp = 0; tp < 9; ++tp) {
-                const unsigned short* ap = xp + (2 * (tp % 3)) * XPLANE + i16 * XS + (w + tp / 3) * TF + 8 * g;
+                const unsigned short* ap = xp + (PLANES * (tp % 3)) * XPLANE + i16 * XS + (w + tp / 3) * TF + 8 * g;
                 ah[tp] = *(const s16x8*)ap;
-                al[tp] = *(const s16x8*)(ap + XPLANE);
+                if constexpr (NP != 1) al[tp] = *(const s16x8*)(ap + XPLANE);
             }
             sed_sched_fence();
 #pragma unroll
@@ -1335,7 +1378,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_alltaps_bf16_kernel(const floa
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) {
                     f32x4 a = acc16[M16 ? tp : 0][nt];
-                    if (WGN_ABL & 1) { a[0] += (float)(al[tp][0] + bh[nt][1] + ah[tp][2] + bl[nt][3]); }
+                    if constexpr (NP == 1) a = mfma16_bf16(ah[tp], bh[nt], a);
+                    else if (WGN_ABL & 1) { a[0] += (float)(al[tp][0] + bh[nt][1] + ah[tp][2] + bl[nt][3]); }
                     else {
                     a = mfma16_bf16(al[tp], bh[nt], a);
                     a = mfma16_bf16(ah[tp], bl[nt], a);
@@ -1353,12 +1397,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_alltaps_bf16_kernel(const floa
                 const int ks = 4 * wk + k4, r = ks >> 1, c0 = 16 * (ks & 1) + 8 * hi;
                 const unsigned short* bp = dp + (32 * wn + lo) * DS + r * TF + c0;
                 bh[buf] = *(const s16x8*)bp;
-                bl[buf] = *(const s16x8*)(bp + DPLANE);
+                if constexpr (NP != 1) bl[buf] = *(const s16x8*)(bp + DPLANE);
 #pragma unroll
                 for (int tp = 0; tp < 9; ++tp) {
-                    const unsigned short* ap = xp + (2 * (tp % 3)) * XPLANE + lo * XS + (r + tp / 3) * TF + c0;
+                    const unsigned short* ap = xp + (PLANES * (tp % 3)) * XPLANE + lo * XS + (r + tp / 3) * TF + c0;
                     ah[buf][tp] = *(const s16x8*)ap;
-                    al[buf][tp] = *(const s16x8*)(ap + XPLANE);
+                    if constexpr (NP != 1) al[buf][tp] = *(const s16x8*)(ap + XPLANE);
                 }
             };
             fetch(0, 0);
@@ -1370,7 +1414,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_alltaps_bf16_kernel(const floa
 #pragma unroll
                 for (int tp = 0; tp < 9; ++tp) {
                     f32x16 a = acc[M16 ? 0 : tp];
-                    if (WGN_ABL & 1) { a[0] += (float)(al[cur][tp][0] + bh[cur][1] + ah[cur][tp][2] + bl[cur][3]); }
+                    if constexpr (NP == 1) a = mfma32_bf16(ah[cur][tp], bh[cur], a);
+                    else if (WGN_ABL & 1) { a[0] += (float)(al[cur][tp][0] + bh[cur][1] + ah[cur][tp][2] + bl[cur][3]); }
                     else {
                     a = mfma32_bf16(al[cur][tp], bh[cur], a);
                     a = mfma32_bf16(ah[cur][tp], bl[cur], a);
@@ -1420,16 +1465,17 @@ __global__ __launch_bounds__(256) void conv_wgrad_alltaps_bf16_kernel(const floa
     __syncthreads();
     for (int idx = threadIdx.x; idx < 9 * CIN * COUT; idx += 256) part[idx] = red[idx];
 }
-template <int CIN, int COUT>
+template <int CIN, int COUT, int NP = 3>
 static int launch_wgrad_alltaps_bf16(const float* x, const float* dy, float* dWp, int B, int T, int F, int grid, hipStream_t s) {
-    using Cfg = WgnCfg<CIN, COUT>;
-    SED_MAX_SMEM((conv_wgrad_alltaps_bf16_kernel<CIN, COUT>), Cfg::SMEM);
-    SED_LAUNCH((conv_wgrad_alltaps_bf16_kernel<CIN, COUT>), dim3(grid), dim3(256), Cfg::SMEM, s, x, dy, dWp, B, T, F);
+    using Cfg = WgnCfg<CIN, COUT, NP>;
+    SED_MAX_SMEM((NP == 1 ? conv_wgrad_alltaps_bf16_kernel<CIN, COUT, SedOneProduct> : conv_wgrad_alltaps_bf16_kernel<CIN, COUT>), Cfg::SMEM);
+    SED_LAUNCH((NP == 1 ? conv_wgrad_alltaps_bf16_kernel<CIN, COUT, SedOneProduct> : conv_wgrad_alltaps_bf16_kernel<CIN, COUT>), dim3(grid), dim3(256), Cfg::SMEM, s, x, dy, dWp, B, T, F);
     return sed_check_launch();
 }
 
 static int conv_wgrad_impl(const float* x, const float* dy, float* dWp, float* dW, int B, int T, int F, int CIN, int COUT,
-                           bool split_bf16, void* stream) {
+                           bool split_bf16, void* stream, bool single = false) {
+    // (single: the one-product twins of the split-bf16 kernels -- same kernel choice, same grids and partial layout)
     hipStream_t s = (hipStream_t)stream;
     int rc = SED_ERR_UNSUPPORTED;
     const int TF = conv_tf(F);
@@ -1441,7 +1487,9 @@ static int conv_wgrad_impl(const float* x, const float* dy, float* dWp, float* d
         // and reduce (18 / 74 KB each: 1024 / 512 partials were 22 / 29 us of fixed cost per launch)
         const int capb = sed_tuning[SED_TUNE_WGRAD_CAP] > 0 ? sed_tuning[SED_TUNE_WGRAD_CAP] : (CIN == 16 ? 512 : 256);
         if (nparts > capb) nparts = capb;
-        if (CIN == 16) rc = launch_wgrad_alltaps_bf16<16, 32>(x, dy, dWp, B, T, F, nparts, s);
+        if (single) rc = CIN == 16 ? launch_wgrad_alltaps_bf16<16, 32, 1>(x, dy, dWp, B, T, F, nparts, s)
+                                   : launch_wgrad_alltaps_bf16<32, 64, 1>(x, dy, dWp, B, T, F, nparts, s);
+        else if (CIN == 16) rc = launch_wgrad_alltaps_bf16<16, 32>(x, dy, dWp, B, T, F, nparts, s);
         else rc = launch_wgrad_alltaps_bf16<32, 64>(x, dy, dWp, B, T, F, nparts, s);
     }
 #define WGA_CASE(ci, co, tf) if (rc != SED_OK && CIN == ci && COUT == co && TF == tf) rc = launch_wgrad_alltaps<ci, co, tf>(x, dy, dWp, B, T, F, s);
@@ -1451,12 +1499,15 @@ static int conv_wgrad_impl(const float* x, const float* dy, float* dWp, float* d
     // wide layers, split-bf16: one kernel row (three taps) per workgroup when a row is whole octets (sed_set_tuning key 9 = 1: one tap)
     if (rc != SED_OK && split_bf16 && wgrad_row_ok(CIN, COUT, F) && sed_tuning[SED_TUNE_WGRAD_WIDE] != 1) {
         nparts = wgrad_row_parts(CIN, B, T, F);
-        if (CIN == 64) rc = launch_wgrad_bf16_row<64, 128, 128>(x, dy, dWp, B, T, F, nparts, s);
+        if (single) rc = CIN == 64 ? launch_wgrad_bf16_row<64, 128, 128, 1>(x, dy, dWp, B, T, F, nparts, s)
+                                   : launch_wgrad_bf16_row<128, 128, 64, 1>(x, dy, dWp, B, T, F, nparts, s);
+        else if (CIN == 64) rc = launch_wgrad_bf16_row<64, 128, 128>(x, dy, dWp, B, T, F, nparts, s);
         else rc = launch_wgrad_bf16_row<128, 128, 64>(x, dy, dWp, B, T, F, nparts, s);
     }
 #define WG_CASE(ci, co)                                                                                        \
     if (rc != SED_OK && CIN == ci && COUT == co)                                                               \
-        rc = split_bf16 ? launch_wgrad_bf16<ci, co>(x, dy, dWp, B, T, F, s) : launch_wgrad<ci, co>(x, dy, dWp, B, T, F, s);
+        rc = single ? launch_wgrad_bf16<ci, co, 1>(x, dy, dWp, B, T, F, s)                                      \
+           : split_bf16 ? launch_wgrad_bf16<ci, co>(x, dy, dWp, B, T, F, s) : launch_wgrad<ci, co>(x, dy, dWp, B, T, F, s);
     WG_CASE(64, 128) WG_CASE(128, 128)
 #undef WG_CASE
     if (rc != SED_OK) return rc;
@@ -1474,6 +1525,12 @@ SED_API int sed_conv_wgrad(const float* x, const float* dy, float* dWp, float* d
 SED_API int sed_conv_wgrad_bf16x3(const float* x, const float* dy, float* dWp, float* dW, int B, int T, int F, int CIN,
                                      int COUT, void* stream) {
     return conv_wgrad_impl(x, dy, dWp, dW, B, T, F, CIN, COUT, true, stream);
+}
+// Same contract and kernel choice with ONE MFMA per product on x and dy rounded once to bf16 (the "bf16" mode); the narrow layers on
+// tiles narrower than 32 columns use the exact-f32 all-taps kernel as above.  Same scratch, same deterministic partial / reduce scheme.
+SED_API int sed_conv_wgrad_bf16x1(const float* x, const float* dy, float* dWp, float* dW, int B, int T, int F, int CIN,
+                                  int COUT, void* stream) {
+    return conv_wgrad_impl(x, dy, dWp, dW, B, T, F, CIN, COUT, true, stream, true);
 }
 
 // ---------------------------------------------------------------------------------------------

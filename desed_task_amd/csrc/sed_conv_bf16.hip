@@ -15,8 +15,12 @@
 
 #define CONVB_THREADS(COUT) ((COUT) >= 64 ? 512 : 256)
 
-template <int CIN, int COUT, int TF, int MP = 128, int CKT = 32>
+// NP = 3: three MFMAs per product on hi / lo planes.  NP = 1 (the "bf16" mode, sed_conv3x3_bf16x1*): both operands rounded once to bf16, one
+// MFMA per product; the lo planes do not exist -- not in the packs, not in LDS (PLANES = 1: half the patch, half the weight row), not read.
+// Tiling and k order are those of NP = 3, so on operands that are bf16 values already the two forms give the same bits.
+template <int CIN, int COUT, int TF, int MP = 128, int CKT = 32, int NP = 3>
 struct ConvBCfg {
+    static constexpr int PLANES = NP == 1 ? 1 : 2;
     static constexpr int TR = MP / TF;
     // PWL = logical patch width; PW = its LDS pitch in pixels.  The A-fragment ds_read_b128 of a wave is served in lane groups
     // {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} (MI355X_MICROARCH.md); with a pixel pitch of RSS / 8 = 5 (3) sixteen-byte slots a group is
@@ -38,11 +42,11 @@ struct ConvBCfg {
     static constexpr int NTW = NT / WN;
     static_assert(NTW >= 1 && NTW * WN == NT, "wave split must tile COUT");
     static_assert(THREADS % (CK / 4) == 0, "a thread keeps one channel quad for all its patch elements");
-    static constexpr int PATCH_S = 2 * PP * RSS;         // shorts: hi plane | lo plane
-    static constexpr int WBUF_S = 2 * NCOL * RSS;        // shorts per weight buffer: hi | lo
+    static constexpr int PATCH_S = PLANES * PP * RSS;    // shorts: hi plane | lo plane
+    static constexpr int WBUF_S = PLANES * NCOL * RSS;   // shorts per weight buffer: hi | lo
     static constexpr int SMEM = (PATCH_S + 3 * WBUF_S) * 2 + 64;    // patch + one kernel row (3 taps) of weight slabs
     static constexpr int SMEM_BNB = SMEM + 4 * CIN * 4;             // + the four per-channel BatchNorm-backward constants
-    static constexpr int SLAB = 2 * COUT * CK;           // shorts per (tap, chunk) slab in global memory
+    static constexpr int SLAB = PLANES * COUT * CK;      // shorts per (tap, chunk) slab in global memory
 };
 
 // W (COUT, CIN, 3, 3) fp32 -> forward slabs Wf[tap][cc][plane][co][ci_local] and data-gradient slabs
@@ -60,6 +64,8 @@ struct PackBJobs {
 // same.  The reads are then strided (36 B resp. 36 CIN B apart: the 2 MB of weights sit in L2); until round 4 the element order of W
 // was walked instead -- coalesced reads, but four 2-byte stores per thread each into a cache line of its own (2.1 M partial-line
 // writes: most of the launch's 12 us, at the head of the step's critical path).
+// PLANES = 1: the single-product packs -- the same slabs with the hi plane only (half the bytes; the buffers keep their size).
+template <int PLANES = 2>
 __device__ __forceinline__ void pack_weights_bf16_one(const PackBJobs& jobs, int i) {
     const int tot = jobs.start[jobs.n];
     const bool dgrad = i >= tot;
@@ -76,20 +82,23 @@ __device__ __forceinline__ void pack_weights_bf16_one(const PackBJobs& jobs, int
         const int co = rem / CIN, ci = rem - co * CIN;
         bf16_split(jobs.W[j][((size_t)co * CIN + ci) * 9 + tap], hi, lo);
         const int CK = jobs.ckf[j], NCH = CIN / CK, cc = ci / CK, cl = ci % CK;
-        unsigned short* d = jobs.Wf[j] + ((size_t)(tap * NCH + cc) * 2 * COUT + co) * CK + cl;
+        unsigned short* d = jobs.Wf[j] + ((size_t)(tap * NCH + cc) * PLANES * COUT + co) * CK + cl;
         d[0] = hi;
-        d[(size_t)COUT * CK] = lo;
+        if (PLANES == 2) d[(size_t)COUT * CK] = lo;
     } else {
         const int ci = rem / COUT, co = rem - ci * COUT;                // tap: the data-gradient slab index (kernel flipped: source tap 8 - tap)
         bf16_split(jobs.W[j][((size_t)co * CIN + ci) * 9 + (8 - tap)], hi, lo);
         const int CK = jobs.ckd[j], NCH = COUT / CK, cc = co / CK, cl = co % CK;
-        unsigned short* d = jobs.Wd[j] + ((size_t)(tap * NCH + cc) * 2 * CIN + ci) * CK + cl;
+        unsigned short* d = jobs.Wd[j] + ((size_t)(tap * NCH + cc) * PLANES * CIN + ci) * CK + cl;
         d[0] = hi;
-        d[(size_t)CIN * CK] = lo;
+        if (PLANES == 2) d[(size_t)CIN * CK] = lo;
     }
 }
 __global__ __launch_bounds__(256) void pack_weights_bf16_kernel(PackBJobs jobs) {
     pack_weights_bf16_one(jobs, blockIdx.x * 256 + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void pack_weights_bf16x1_kernel(PackBJobs jobs) {
+    pack_weights_bf16_one<1>(jobs, blockIdx.x * 256 + threadIdx.x);
 }
 // The CNN's prologue in ONE launch (round 4): everything a forward needs before its first convolution and that depends on nothing
 // but the weights, a seed and the input -- the weight packs (blocks [0, pack_blocks)), the SpecAugment bands of the batch (one block)
@@ -101,9 +110,30 @@ struct PrologueExtra {
     const float4* src; float4* dst; size_t n4; const float* src_tail; float* dst_tail; int ntail;
     int pack_blocks, copy_blocks;
 };
+template <int PLANES>
+__device__ __forceinline__ void cnn_prologue_body(const PackBJobs& jobs, const PrologueExtra& ex);
+__global__ __launch_bounds__(256) void cnn_prologue_bf16x1_kernel(PackBJobs jobs, PrologueExtra ex) { cnn_prologue_body<1>(jobs, ex); }
 __global__ __launch_bounds__(256) void cnn_prologue_bf16_kernel(PackBJobs jobs, PrologueExtra ex) {
     const int blk = blockIdx.x;
     if (blk < ex.pack_blocks) { pack_weights_bf16_one(jobs, blk * 256 + threadIdx.x); return; }
+    if (blk == ex.pack_blocks) {
+        if (ex.bounds) {
+            const uint32_t seed = ex.seed + (ex.seed_dev ? *ex.seed_dev : 0u);
+            for (int b = threadIdx.x; b < ex.B; b += 256) sed_specaug_draw(ex.bounds, b, ex.nb, ex.f_param, ex.n_freq, ex.t_param, ex.n_time, seed);
+        }
+        if ((int)threadIdx.x < ex.ntail) ex.dst_tail[threadIdx.x] = ex.src_tail[threadIdx.x];
+        return;
+    }
+    const size_t stride = (size_t)ex.copy_blocks * 256;
+    for (size_t i = (size_t)(blk - ex.pack_blocks - 1) * 256 + threadIdx.x; i < ex.n4; i += stride) ex.dst[i] = ex.src[i];
+}
+template <int PLANES>
+// (The body of cnn_prologue_bf16_kernel once more, as a template on the plane count.  The kernel above does NOT call it: with its body
+//  moved into this function the compiler emits other instructions for it -- compared on the gfx950 disassembly -- and the three-product
+//  kernels are to stay as they were.)
+__device__ __forceinline__ void cnn_prologue_body(const PackBJobs& jobs, const PrologueExtra& ex) {
+    const int blk = blockIdx.x;
+    if (blk < ex.pack_blocks) { pack_weights_bf16_one<PLANES>(jobs, blk * 256 + threadIdx.x); return; }
     if (blk == ex.pack_blocks) {
         if (ex.bounds) {
             const uint32_t seed = ex.seed + (ex.seed_dev ? *ex.seed_dev : 0u);
@@ -151,11 +181,21 @@ SED_API int sed_conv_pack_multi_bf16(int n, const void* const* W, void* const* W
     SED_LAUNCH(pack_weights_bf16_kernel, dim3((tot + 255) / 256), dim3(256), 0, (hipStream_t)stream, jobs);
     return sed_check_launch();
 }
+// The single-product packs (hi plane only) for sed_conv3x3_bf16x1 / _bnbwd: same arguments, same buffer sizes (the second half of each
+// buffer is not written).
+SED_API int sed_conv_pack_multi_bf16x1(int n, const void* const* W, void* const* Wf, void* const* Wd, const int* cout,
+                                       const int* cin, void* stream) {
+    if (n < 1 || n > 8) return SED_ERR_ARG;
+    PackBJobs jobs;
+    const int tot = packb_jobs(jobs, n, W, Wf, Wd, cout, cin) * (packb_any_dgrad(jobs) ? 2 : 1);
+    SED_LAUNCH(pack_weights_bf16x1_kernel, dim3((tot + 255) / 256), dim3(256), 0, (hipStream_t)stream, jobs);
+    return sed_check_launch();
+}
 // The same packs + (bounds != null) the seeded SpecAugment bands of sed_specaug_bounds_seeded + (copy_dst != null) copy_n floats
 // copy_src -> copy_dst (both 16-byte aligned), one launch.  n == 0: no packs.
-SED_API int sed_cnn_prologue_bf16(int n, const void* const* W, void* const* Wf, void* const* Wd, const int* cout, const int* cin,
-                                     int* bounds, int B, int nb, int f_param, int n_freq, int t_param, int n_time, unsigned seed,
-                                     const unsigned* seed_dev, const float* copy_src, float* copy_dst, long long copy_n, void* stream) {
+static int cnn_prologue_impl(bool single, int n, const void* const* W, void* const* Wf, void* const* Wd, const int* cout, const int* cin,
+                            int* bounds, int B, int nb, int f_param, int n_freq, int t_param, int n_time, unsigned seed,
+                            const unsigned* seed_dev, const float* copy_src, float* copy_dst, long long copy_n, void* stream) {
     if (n < 0 || n > 8) return SED_ERR_ARG;
     if (bounds && B > 0 && nb != 1 && nb != B) return SED_ERR_ARG;
     if (copy_dst && (!copy_src || copy_n < 0 || ((uintptr_t)copy_src & 15) || ((uintptr_t)copy_dst & 15))) return SED_ERR_ARG;
@@ -173,8 +213,22 @@ SED_API int sed_cnn_prologue_bf16(int n, const void* const* W, void* const* Wf, 
     size_t cb = (n4 + 1023) / 1024;
     ex.copy_blocks = (int)(cb > 4096 ? 4096 : cb);
     if (ex.pack_blocks == 0 && !ex.bounds && n4 == 0 && ex.ntail == 0) return SED_OK;
-    SED_LAUNCH(cnn_prologue_bf16_kernel, dim3(ex.pack_blocks + 1 + ex.copy_blocks), dim3(256), 0, (hipStream_t)stream, jobs, ex);
+    if (single) SED_LAUNCH(cnn_prologue_bf16x1_kernel, dim3(ex.pack_blocks + 1 + ex.copy_blocks), dim3(256), 0, (hipStream_t)stream, jobs, ex);
+    else SED_LAUNCH(cnn_prologue_bf16_kernel, dim3(ex.pack_blocks + 1 + ex.copy_blocks), dim3(256), 0, (hipStream_t)stream, jobs, ex);
     return sed_check_launch();
+}
+SED_API int sed_cnn_prologue_bf16(int n, const void* const* W, void* const* Wf, void* const* Wd, const int* cout, const int* cin,
+                                     int* bounds, int B, int nb, int f_param, int n_freq, int t_param, int n_time, unsigned seed,
+                                     const unsigned* seed_dev, const float* copy_src, float* copy_dst, long long copy_n, void* stream) {
+    return cnn_prologue_impl(false, n, W, Wf, Wd, cout, cin, bounds, B, nb, f_param, n_freq, t_param, n_time, seed, seed_dev, copy_src,
+                             copy_dst, copy_n, stream);
+}
+// The same prologue with the single-product packs of sed_conv_pack_multi_bf16x1.
+SED_API int sed_cnn_prologue_bf16x1(int n, const void* const* W, void* const* Wf, void* const* Wd, const int* cout, const int* cin,
+                                    int* bounds, int B, int nb, int f_param, int n_freq, int t_param, int n_time, unsigned seed,
+                                    const unsigned* seed_dev, const float* copy_src, float* copy_dst, long long copy_n, void* stream) {
+    return cnn_prologue_impl(true, n, W, Wf, Wd, cout, cin, bounds, B, nb, f_param, n_freq, t_param, n_time, seed, seed_dev, copy_src,
+                             copy_dst, copy_n, stream);
 }
 
 // CONVB_ABL: timing-ablation mask for tools/convb_variants.py (0 in the product build): 1 = no weight-slab global loads,
@@ -217,13 +271,14 @@ __device__ __forceinline__ void conv_lane_pixel(int i, int& prow, int& pcol) {
     else { prow = gsel + 2 * (g / TF); pcol = g % TF; }
 }
 
-template <int CIN, int COUT, int TF, bool STATS, int MP = 128, int CKT = 32, bool BNB = false>
+template <int CIN, int COUT, int TF, bool STATS, int MP = 128, int CKT = 32, bool BNB = false, class... ONE>
 __global__ __launch_bounds__(CONVB_THREADS(COUT)) void conv3x3_bf16_kernel(const float* __restrict__ x,
                                                                             const unsigned short* __restrict__ Wp,
                                                                             const float* __restrict__ bias, float* __restrict__ y,
                                                                             float* __restrict__ partial, int B, int T, int F,
                                                                             ConvBnb bnb) {
-    using Cfg = ConvBCfg<CIN, COUT, TF, MP, CKT>;
+    constexpr int NP = sed_np<ONE...>();
+    using Cfg = ConvBCfg<CIN, COUT, TF, MP, CKT, NP>;
     constexpr int TR = Cfg::TR, PW = Cfg::PW, PWL = Cfg::PWL, PP = Cfg::PP, PPL = Cfg::PPL, CK = Cfg::CK, RSS = Cfg::RSS, NCH = Cfg::NCH, NT = Cfg::NT,
                   NTW = Cfg::NTW, THREADS = Cfg::THREADS, WM = Cfg::WM, NCOL = Cfg::NCOL, SLAB = Cfg::SLAB, WBUF_S = Cfg::WBUF_S;
     SED_DYN_SMEM(smem_raw);
@@ -358,11 +413,15 @@ __global__ __launch_bounds__(CONVB_THREADS(COUT)) void conv3x3_bf16_kernel(const
                             *(float4*)(bnb.dy_out + (((size_t)b * T + t) * F + f) * CIN + cc * CK + 4 * v) = g;
                     }
                 }
+                if constexpr (NP == 1) {        // rounded once: no lo plane
+                    *(uint2*)(patch + pix * RSS + 4 * v) = make_uint2(bf16_round2(ld[u].x, ld[u].y), bf16_round2(ld[u].z, ld[u].w));
+                } else {
                 uint2 hv, lv;
                 bf16_split2(ld[u].x, ld[u].y, hv.x, lv.x);
                 bf16_split2(ld[u].z, ld[u].w, hv.y, lv.y);
                 *(uint2*)(patch + pix * RSS + 4 * v) = hv;
                 *(uint2*)(patch + PP * RSS + pix * RSS + 4 * v) = lv;
+                }
             }
         }
     };
@@ -395,6 +454,13 @@ __global__ __launch_bounds__(CONVB_THREADS(COUT)) void conv3x3_bf16_kernel(const
                 const unsigned short* ap = patch + abase + (r * PW + t3) * RSS;
 #pragma unroll
                 for (int ks = 0; ks < CK / 16; ++ks) {
+                    if constexpr (NP == 1) {
+                        const s16x8 a1 = *(const s16x8*)(ap + 16 * ks);
+#pragma unroll
+                        for (int nt = 0; nt < NTW; ++nt)
+                            acc[nt] = mfma32_bf16(a1, *(const s16x8*)(wb + ((wn * NTW + nt) * 32 + lo) * RSS + 16 * ks + 8 * hi), acc[nt]);
+                        continue;
+                    }
                     s16x8 a_hi, a_lo;
                     if (CONVB_ABL & 16) { a_hi = (s16x8)(short)(lane + ks); a_lo = (s16x8)(short)(lane + t3); }
                     else { a_hi = *(const s16x8*)(ap + 16 * ks); a_lo = *(const s16x8*)(ap + PP * RSS + 16 * ks); }
@@ -496,28 +562,32 @@ static inline int convb_persistent_grid(K kern, int threads, int smem, int ntile
 #endif
 }
 
-template <int CIN, int COUT, int TF, int MP = 128, int CKT = 32, bool BNB = false>
+template <int CIN, int COUT, int TF, bool STATS, int MP, int CKT, bool BNB, int NP>
+struct ConvKern {           // the kernel of a product count
+    static constexpr auto fn = NP == 1 ? conv3x3_bf16_kernel<CIN, COUT, TF, STATS, MP, CKT, BNB, SedOneProduct> : conv3x3_bf16_kernel<CIN, COUT, TF, STATS, MP, CKT, BNB>;
+};
+template <int CIN, int COUT, int TF, int MP = 128, int CKT = 32, bool BNB = false, int NP = 3>
 static int launch_convb(const float* x, const unsigned short* Wp, const float* bias, float* y, float* partial, int B, int T, int F,
                         hipStream_t s, ConvBnb bnb = ConvBnb()) {
-    using Cfg = ConvBCfg<CIN, COUT, TF, MP, CKT>;
+    using Cfg = ConvBCfg<CIN, COUT, TF, MP, CKT, NP>;
     const int ntiles = B * ((T + Cfg::TR - 1) / Cfg::TR) * (F / TF);
     if constexpr (BNB) {
         if constexpr (CIN >= COUT) {         // data gradients only (a block's convolution never narrows in the forward direction)
-            SED_MAX_SMEM((conv3x3_bf16_kernel<CIN, COUT, TF, false, MP, CKT, true>), Cfg::SMEM_BNB);
-            const int nblk = convb_persistent_grid(conv3x3_bf16_kernel<CIN, COUT, TF, false, MP, CKT, true>, Cfg::THREADS, Cfg::SMEM_BNB, ntiles, CIN);
-            SED_LAUNCH((conv3x3_bf16_kernel<CIN, COUT, TF, false, MP, CKT, true>), dim3(nblk), dim3(Cfg::THREADS), Cfg::SMEM_BNB, s, x, Wp, bias, y, partial, B, T, F, bnb);
+            SED_MAX_SMEM((ConvKern<CIN, COUT, TF, false, MP, CKT, true, NP>::fn), Cfg::SMEM_BNB);
+            const int nblk = convb_persistent_grid(ConvKern<CIN, COUT, TF, false, MP, CKT, true, NP>::fn, Cfg::THREADS, Cfg::SMEM_BNB, ntiles, CIN);
+            SED_LAUNCH((ConvKern<CIN, COUT, TF, false, MP, CKT, true, NP>::fn), dim3(nblk), dim3(Cfg::THREADS), Cfg::SMEM_BNB, s, x, Wp, bias, y, partial, B, T, F, bnb);
             return sed_check_launch();
         } else {
             return SED_ERR_UNSUPPORTED;
         }
     } else if (partial) {
-        SED_MAX_SMEM((conv3x3_bf16_kernel<CIN, COUT, TF, true, MP, CKT>), Cfg::SMEM);
-        const int nblk = convb_persistent_grid(conv3x3_bf16_kernel<CIN, COUT, TF, true, MP, CKT>, Cfg::THREADS, Cfg::SMEM, ntiles, CIN);
-        SED_LAUNCH((conv3x3_bf16_kernel<CIN, COUT, TF, true, MP, CKT>), dim3(nblk), dim3(Cfg::THREADS), Cfg::SMEM, s, x, Wp, bias, y, partial, B, T, F, bnb);
+        SED_MAX_SMEM((ConvKern<CIN, COUT, TF, true, MP, CKT, false, NP>::fn), Cfg::SMEM);
+        const int nblk = convb_persistent_grid(ConvKern<CIN, COUT, TF, true, MP, CKT, false, NP>::fn, Cfg::THREADS, Cfg::SMEM, ntiles, CIN);
+        SED_LAUNCH((ConvKern<CIN, COUT, TF, true, MP, CKT, false, NP>::fn), dim3(nblk), dim3(Cfg::THREADS), Cfg::SMEM, s, x, Wp, bias, y, partial, B, T, F, bnb);
     } else {
-        SED_MAX_SMEM((conv3x3_bf16_kernel<CIN, COUT, TF, false, MP, CKT>), Cfg::SMEM);
-        const int nblk = convb_persistent_grid(conv3x3_bf16_kernel<CIN, COUT, TF, false, MP, CKT>, Cfg::THREADS, Cfg::SMEM, ntiles, CIN);
-        SED_LAUNCH((conv3x3_bf16_kernel<CIN, COUT, TF, false, MP, CKT>), dim3(nblk), dim3(Cfg::THREADS), Cfg::SMEM, s, x, Wp, bias, y, partial, B, T, F, bnb);
+        SED_MAX_SMEM((ConvKern<CIN, COUT, TF, false, MP, CKT, false, NP>::fn), Cfg::SMEM);
+        const int nblk = convb_persistent_grid(ConvKern<CIN, COUT, TF, false, MP, CKT, false, NP>::fn, Cfg::THREADS, Cfg::SMEM, ntiles, CIN);
+        SED_LAUNCH((ConvKern<CIN, COUT, TF, false, MP, CKT, false, NP>::fn), dim3(nblk), dim3(Cfg::THREADS), Cfg::SMEM, s, x, Wp, bias, y, partial, B, T, F, bnb);
     }
     return sed_check_launch();
 }
@@ -541,7 +611,7 @@ SED_API int sed_conv_fwd_blocks_bf16(int B, int T, int F, int CIN, int COUT) {
     return B * ((T + TR - 1) / TR) * (F / TF);
 }
 
-template <bool BNB>
+template <bool BNB, int NP = 3>
 static int convb_dispatch(const float* x, const void* Wp, const float* bias, float* y, float* partial, int B, int T, int F,
                           int CIN, int COUT, hipStream_t s, ConvBnb bnb) {
     if (B <= 0 || T <= 0) return SED_OK;
@@ -551,7 +621,7 @@ static int convb_dispatch(const float* x, const void* Wp, const float* bias, flo
     const int MP = convb_mp(F, CIN, COUT);
     const int CK = CIN >= 32 ? convb_ck(CIN, COUT) : 32;      // narrower inputs are a single chunk either way
 #define CONVB_CASE16(ci, co, tf, mp) \
-    if (CIN == ci && COUT == co && TF == tf && MP == mp && CK == 16) return launch_convb<ci, co, tf, mp, 16, BNB>(x, W, bias, y, partial, B, T, F, s, bnb);
+    if (CIN == ci && COUT == co && TF == tf && MP == mp && CK == 16) return launch_convb<ci, co, tf, mp, 16, BNB, NP>(x, W, bias, y, partial, B, T, F, s, bnb);
     // 16-channel weight chunks (half the LDS per workgroup): the wide production shapes
     CONVB_CASE16(32, 64, 32, 128) CONVB_CASE16(64, 128, 16, 128) CONVB_CASE16(64, 128, 16, 256)
     CONVB_CASE16(128, 128, 8, 128) CONVB_CASE16(128, 128, 8, 256) CONVB_CASE16(128, 128, 4, 64) CONVB_CASE16(128, 128, 4, 128)
@@ -563,7 +633,7 @@ static int convb_dispatch(const float* x, const void* Wp, const float* bias, flo
 #undef CONVB_CASE16
     if (CK == 16) return SED_ERR_UNSUPPORTED;
 #define CONVB_CASE(ci, co, tf, mp) \
-    if (CIN == ci && COUT == co && TF == tf && MP == mp) return launch_convb<ci, co, tf, mp, 32, BNB>(x, W, bias, y, partial, B, T, F, s, bnb);
+    if (CIN == ci && COUT == co && TF == tf && MP == mp) return launch_convb<ci, co, tf, mp, 32, BNB, NP>(x, W, bias, y, partial, B, T, F, s, bnb);
     // production shapes of the 2023 recipe (forward, then data gradient)
     CONVB_CASE(16, 32, 32, 128)
     CONVB_CASE(32, 64, 32, 128) CONVB_CASE(32, 64, 32, 256)
@@ -599,4 +669,21 @@ SED_API int sed_conv3x3_bf16x3_bnbwd(const float* dz, const float* ybn, const fl
     bnb.ybn = ybn; bnb.stats = stats; bnb.gamma = gamma; bnb.dgamma = dgamma; bnb.dbeta = dbeta; bnb.dy_out = dy_out; bnb.dbias = dbias;
     bnb.inv_count = 1.0f / (float)((size_t)B * T * F);
     return convb_dispatch<true>(dz, Wd, nullptr, dx, nullptr, B, T, F, CIN, COUT, (hipStream_t)stream, bnb);
+}
+
+// ---- the single-product ("bf16") twins: same contracts with the packs of sed_conv_pack_multi_bf16x1 / sed_cnn_prologue_bf16x1; both
+// operands rounded once to bf16 (round-to-nearest-even), one MFMA per product, fp32 accumulate, bias / statistics epilogue in fp32.  In the
+// BN-folded form the dy that is FORMED is rounded once for the MFMA; the fp32 dy written to dy_out is the three-product entry's, bit for bit.
+SED_API int sed_conv3x3_bf16x1(const float* x, const void* Wp, const float* bias, float* y, float* partial, int B, int T, int F,
+                               int CIN, int COUT, void* stream) {
+    return convb_dispatch<false, 1>(x, Wp, bias, y, partial, B, T, F, CIN, COUT, (hipStream_t)stream, ConvBnb());
+}
+SED_API int sed_conv3x3_bf16x1_bnbwd(const float* dz, const float* ybn, const float* stats, const float* gamma, const float* dgamma,
+                                     const float* dbeta, const void* Wd, float* dx, float* dy_out, float* dbias, int B, int T, int F,
+                                     int CIN, int COUT, void* stream) {
+    if (!dz || !ybn || !stats || !gamma || !dgamma || !dbeta || !dy_out || dy_out == dz) return SED_ERR_ARG;
+    ConvBnb bnb;
+    bnb.ybn = ybn; bnb.stats = stats; bnb.gamma = gamma; bnb.dgamma = dgamma; bnb.dbeta = dbeta; bnb.dy_out = dy_out; bnb.dbias = dbias;
+    bnb.inv_count = 1.0f / (float)((size_t)B * T * F);
+    return convb_dispatch<true, 1>(dz, Wd, nullptr, dx, nullptr, B, T, F, CIN, COUT, (hipStream_t)stream, bnb);
 }

@@ -22,6 +22,7 @@ __device__ __forceinline__ void split4(const float4 v, uint2& h, uint2& l) {
     bf16_split2(v.x, v.y, h.x, l.x);
     bf16_split2(v.z, v.w, h.y, l.y);
 }
+__device__ __forceinline__ uint2 round4(const float4 v) { return make_uint2(bf16_round2(v.x, v.y), bf16_round2(v.z, v.w)); }
 
 // One operand tile of ROWS rows x 32 k.  KC = true: element (row, k) at base[row * ld + k]; false: base[k * ld + row].
 // NV float4 per thread.  load(): global -> registers (zero outside [0, nrows) x [k0, kend)); store(): registers -> LDS planes.
@@ -53,15 +54,17 @@ struct OperandTile {
             }
         }
     }
+    // LO = false (the single-product instantiations): the operand is rounded once, the lo plane is neither formed nor stored
+    template <bool LO = true>
     __device__ __forceinline__ void store(unsigned short* __restrict__ hi_plane, unsigned short* __restrict__ lo_plane, int tid) const {
         if (KC) {
 #pragma unroll
             for (int u = 0; u < NV; ++u) {
                 const int i = tid + 256 * u, row = kc_row(i), kq = i & 7;
                 uint2 h, l;
-                split4(r[u], h, l);
+                if constexpr (LO) split4(r[u], h, l); else h = round4(r[u]);
                 *(uint2*)(hi_plane + row * GB_RS + 4 * kq) = h;
-                *(uint2*)(lo_plane + row * GB_RS + 4 * kq) = l;
+                if constexpr (LO) *(uint2*)(lo_plane + row * GB_RS + 4 * kq) = l;
             }
         } else {
 #pragma unroll
@@ -70,8 +73,14 @@ struct OperandTile {
                 const int rq = rest % (ROWS / 4), kph = rest / (ROWS / 4);
                 const int k = 2 * (kp + 4 * kph);
                 uint2 h0, l0, h1, l1;                          // rows 4rq..4rq+3 at k (r[u]) and k+1 (r[u+1])
-                split4(r[u], h0, l0);
-                split4(r[u + 1], h1, l1);
+                if constexpr (LO) {
+                    split4(r[u], h0, l0);
+                    split4(r[u + 1], h1, l1);
+                } else {
+                    h0 = round4(r[u]);
+                    h1 = round4(r[u + 1]);
+                    l0 = l1 = make_uint2(0u, 0u);
+                }
                 const unsigned hk[4] = {h0.x & 0xFFFFu, h0.x >> 16, h0.y & 0xFFFFu, h0.y >> 16};
                 const unsigned hk1[4] = {h1.x & 0xFFFFu, h1.x >> 16, h1.y & 0xFFFFu, h1.y >> 16};
                 const unsigned lk[4] = {l0.x & 0xFFFFu, l0.x >> 16, l0.y & 0xFFFFu, l0.y >> 16};
@@ -79,7 +88,7 @@ struct OperandTile {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     *(unsigned*)(hi_plane + (4 * rq + j) * GB_RS + k) = hk[j] | (hk1[j] << 16);
-                    *(unsigned*)(lo_plane + (4 * rq + j) * GB_RS + k) = lk[j] | (lk1[j] << 16);
+                    if constexpr (LO) *(unsigned*)(lo_plane + (4 * rq + j) * GB_RS + k) = lk[j] | (lk1[j] << 16);
                 }
             }
         }
@@ -88,7 +97,10 @@ struct OperandTile {
 
 // (waves-per-SIMD hint 3: without it the allocator spreads the accumulators over 64 AGPRs next to 180 VGPRs -- two workgroups per CU;
 //  with it 141 - 168 registers, no AGPRs, no spills: three workgroups per CU.  BEATs linears 17.16 -> 15.49 ms per 48 clips, same box.)
-template <int TA, int TB, int NTN>
+// NP = 3: the split-bf16 products above.  NP = 1 (the "bf16" mode, the *_bf16x1 entries): both operands rounded once to bf16, ONE MFMA per
+// product -- same tile, same k order, no lo planes (half the LDS: 15 / 20 KB, half the staging stores and fragment reads).  With operands
+// that are already bf16 values the two forms give the same bits: lo = 0 adds exact zeros to the same hi*hi chain.
+template <int TA, int TB, int NTN, class... ONE>
 __global__ __launch_bounds__(256, 3) void gemm_bf16x3_kernel(const float* __restrict__ A, const float* __restrict__ Bm,
                                                           const float* __restrict__ bias, float* __restrict__ Cm, int M, int N, int K,
                                                           int lda, int ldb, int ldc, int k_per_slice, int atomic,
@@ -97,9 +109,11 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16x3_kernel(const float* __rest
                                                           const float* __restrict__ Bsw, int ksw, int act, float* __restrict__ part,
                                                           int walk_nt) {
     // Bsw != null: K-concatenated B -- rows k >= ksw come from Bsw (already offset by -ksw rows); ksw % 32 == 0
+    constexpr int NP = sed_np<ONE...>();
     constexpr int BM = GB_BM, BN = 32 * NTN, BK = GB_BK, RS = GB_RS;
-    __shared__ __attribute__((aligned(16))) unsigned short As[2 * BM * RS];     // hi plane, lo plane
-    __shared__ __attribute__((aligned(16))) unsigned short Bs[2 * BN * RS];
+    constexpr int PLANES = NP == 1 ? 1 : 2;
+    __shared__ __attribute__((aligned(16))) unsigned short As[PLANES * BM * RS];     // hi plane, lo plane
+    __shared__ __attribute__((aligned(16))) unsigned short Bs[PLANES * BN * RS];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, lo = lane & 31, hi = lane >> 5;
     // walk_nt > 0 (the BEATs linears: one problem, no K slices, 1-D grid): XCD-aware tile walk.  Workgroup g runs on XCD g & 7; with
     // the N tile as the fastest grid index the walk_nt workgroups that share a 128-row panel of A sat on as many XCDs, each L2 fetched
@@ -127,14 +141,19 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16x3_kernel(const float* __rest
     if (kbeg < kend) { ta.load(A, lda, m0, M, kbeg, kend, tid); tb.load((Bsw && kbeg >= ksw) ? Bsw : Bm, ldb, n0, N, kbeg, kend, tid); }
     for (int k0 = kbeg; k0 < kend; k0 += BK) {
         __syncthreads();                 // everyone finished reading the previous tile
-        ta.store(As, As + BM * RS, tid);
-        tb.store(Bs, Bs + BN * RS, tid);
+        ta.template store<NP != 1>(As, As + BM * RS, tid);
+        tb.template store<NP != 1>(Bs, Bs + BN * RS, tid);
         __syncthreads();
         if (k0 + BK < kend) { ta.load(A, lda, m0, M, k0 + BK, kend, tid); tb.load((Bsw && k0 + BK >= ksw) ? Bsw : Bm, ldb, n0, N, k0 + BK, kend, tid); }
         const unsigned short* ap = As + (32 * w + lo) * RS + 8 * hi;
 #pragma unroll
         for (int ks = 0; ks < BK / 16; ++ks) {
             const s16x8 a_hi = *(const s16x8*)(ap + 16 * ks);
+            if constexpr (NP == 1) {
+#pragma unroll
+                for (int nt = 0; nt < NTN; ++nt)
+                    acc[nt] = mfma32_bf16(a_hi, *(const s16x8*)(Bs + (nt * 32 + lo) * RS + 16 * ks + 8 * hi), acc[nt]);
+            } else {
             const s16x8 a_lo = *(const s16x8*)(ap + BM * RS + 16 * ks);
 #pragma unroll
             for (int nt = 0; nt < NTN; ++nt) {
@@ -144,6 +163,7 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16x3_kernel(const float* __rest
                 acc[nt] = mfma32_bf16(a_lo, b_hi, acc[nt]);
                 acc[nt] = mfma32_bf16(a_hi, b_lo, acc[nt]);
                 acc[nt] = mfma32_bf16(a_hi, b_hi, acc[nt]);
+            }
             }
         }
     }
@@ -178,7 +198,7 @@ SED_API int sed_gemm_pair(const float* A0, const float* A1, const float* B0, con
 static int gemmb_dispatch(const float* A, const float* Bm, const float* bias, float* Cm, const float* A1, const float* B1,
                           const float* bias1, float* C1, int nbatch, int M, int N, int K, int lda, int ldb, int ldc, int transA,
                           int transB, int split_k, int accumulate, hipStream_t s, const float* Bsw = nullptr, int ksw = 0, int act = 0,
-                          float* part = nullptr, bool act_linear = false) {
+                          float* part = nullptr, bool act_linear = false, bool single = false) {
     if (M <= 0 || N <= 0 || K <= 0) return SED_OK;
     bool ok = ((uintptr_t)A % 16 == 0) && ((uintptr_t)Bm % 16 == 0) && lda % 4 == 0 && ldb % 4 == 0 &&
               ((transA ? M : K) % 4 == 0) && ((transB ? K : N) % 4 == 0) && !(transA && transB);
@@ -211,6 +231,11 @@ static int gemmb_dispatch(const float* A, const float* Bm, const float* bias, fl
         walk_nt = (int)grid.x;
         grid = dim3(grid.x * ((grid.y + 7) / 8) * 8, 1, 1);
     }
+    // (single: the one-product twins -- the same tile and slice choice, so that an entry and its twin walk K in the same order)
+#define GEMMB_CASE(ta, tb, nn) \
+    if (single && transA == ta && transB == tb && ntn == nn) { SED_LAUNCH((gemm_bf16x3_kernel<ta, tb, nn, SedOneProduct>), grid, dim3(256), 0, s, A, Bm, bias, Cm, M, N, K, lda, ldb, ldc, kps, atomic, A1, B1, bias1, C1, nbatch, Bsw, ksw, act, part, walk_nt); return sed_check_launch(); }
+    GEMMB_CASE(0, 0, 2) GEMMB_CASE(0, 0, 4) GEMMB_CASE(0, 1, 2) GEMMB_CASE(0, 1, 3) GEMMB_CASE(0, 1, 4) GEMMB_CASE(1, 0, 2) GEMMB_CASE(1, 0, 4)
+#undef GEMMB_CASE
 #define GEMMB_CASE(ta, tb, nn) \
     if (transA == ta && transB == tb && ntn == nn) { SED_LAUNCH((gemm_bf16x3_kernel<ta, tb, nn>), grid, dim3(256), 0, s, A, Bm, bias, Cm, M, N, K, lda, ldb, ldc, kps, atomic, A1, B1, bias1, C1, nbatch, Bsw, ksw, act, part, walk_nt); return sed_check_launch(); }
     GEMMB_CASE(0, 0, 2) GEMMB_CASE(0, 0, 4) GEMMB_CASE(0, 1, 2) GEMMB_CASE(0, 1, 3) GEMMB_CASE(0, 1, 4) GEMMB_CASE(1, 0, 2) GEMMB_CASE(1, 0, 4)
@@ -310,6 +335,68 @@ SED_API int sed_gemm_kcat_splitk_bf16x3(const float* A, const float* B0, const f
     hipStream_t s = (hipStream_t)stream;
     const int rc = gemmb_dispatch(A, B0, nullptr, Cm, nullptr, nullptr, nullptr, nullptr, 1, M, N, K, lda, ldb, ldc, 0, 0, split_k, 0, s,
                                   B1 - (size_t)ksplit * ldb, ksplit, 0, scratch);
+    if (rc != SED_OK) return rc;
+    SED_LAUNCH(splitk_reduce_kernel, dim3((M * N / 4 + 255) / 256, 1), dim3(256), 0, s, (const float*)scratch, Cm, Cm,
+               splitk_slices(K, split_k), M, N, ldc);
+    return sed_check_launch();
+}
+
+// ---- the single-product ("bf16") twins of the six entries above: the same contracts, tiles, slices and reduce, one MFMA per product on
+// operands rounded once to bf16 (gemm_bf16x3_kernel<.., SedOneProduct>).  Operands that miss the 16-byte requirements take the exact-f32
+// fall-back like their twins (plain and pair) or are refused (the others).
+SED_API int sed_gemm_bf16x1(const float* A, const float* Bm, const float* bias, float* Cm, int M, int N, int K, int lda, int ldb,
+                            int ldc, int transA, int transB, int split_k, int accumulate, void* stream) {
+    return gemmb_dispatch(A, Bm, bias, Cm, nullptr, nullptr, nullptr, nullptr, 1, M, N, K, lda, ldb, ldc, transA, transB, split_k,
+                          accumulate, (hipStream_t)stream, nullptr, 0, 0, nullptr, false, true);
+}
+SED_API int sed_gemm_pair_bf16x1(const float* A0, const float* A1, const float* B0, const float* B1, const float* bias0,
+                                 const float* bias1, float* C0, float* C1, int M, int N, int K, int lda, int ldb, int ldc,
+                                 int transA, int transB, int split_k, int accumulate, void* stream) {
+    return gemmb_dispatch(A0, B0, bias0, C0, A1, B1, bias1, C1, 2, M, N, K, lda, ldb, ldc, transA, transB, split_k, accumulate,
+                          (hipStream_t)stream, nullptr, 0, 0, nullptr, false, true);
+}
+SED_API int sed_gemm_pair_splitk_bf16x1(const float* A0, const float* A1, const float* B0, const float* B1, float* C0, float* C1,
+                                        int M, int N, int K, int lda, int ldb, int ldc, int transA, int transB, int split_k,
+                                        float* scratch, void* stream) {
+    if (M <= 0 || N <= 0) return SED_OK;
+    if (!scratch || N % 4 != 0 || ldc % 4 != 0 || K <= 0) return SED_ERR_ARG;
+    if ((((uintptr_t)C0 | (uintptr_t)C1) & 15) != 0) return SED_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = gemmb_dispatch(A0, B0, nullptr, C0, A1, B1, nullptr, C1, 2, M, N, K, lda, ldb, ldc, transA, transB, split_k, 0, s,
+                                  nullptr, 0, 0, scratch, false, true);
+    if (rc != SED_OK) return rc;
+    SED_LAUNCH(splitk_reduce_kernel, dim3((M * N / 4 + 255) / 256, 2), dim3(256), 0, s, (const float*)scratch, C0, C1,
+               splitk_slices(K, split_k), M, N, ldc);
+    return sed_check_launch();
+}
+SED_API int sed_gemm_splitk_bf16x1(const float* A, const float* Bm, float* Cm, int M, int N, int K, int lda, int ldb, int ldc,
+                                   int transA, int transB, int split_k, float* scratch, void* stream) {
+    if (M <= 0 || N <= 0) return SED_OK;
+    if (!scratch || N % 4 != 0 || ldc % 4 != 0 || K <= 0) return SED_ERR_ARG;
+    if (((uintptr_t)Cm & 15) != 0) return SED_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = gemmb_dispatch(A, Bm, nullptr, Cm, nullptr, nullptr, nullptr, nullptr, 1, M, N, K, lda, ldb, ldc, transA, transB,
+                                  split_k, 0, s, nullptr, 0, 0, scratch, false, true);
+    if (rc != SED_OK) return rc;
+    SED_LAUNCH(splitk_reduce_kernel, dim3((M * N / 4 + 255) / 256, 1), dim3(256), 0, s, (const float*)scratch, Cm, Cm,
+               splitk_slices(K, split_k), M, N, ldc);
+    return sed_check_launch();
+}
+SED_API int sed_gemm_kcat_bf16x1(const float* A, const float* B0, const float* B1, float* Cm, int M, int N, int K, int ksplit,
+                                 int lda, int ldb, int ldc, void* stream) {
+    if (ksplit % 32 != 0 || ksplit <= 0 || ksplit >= K) return SED_ERR_ARG;
+    return gemmb_dispatch(A, B0, nullptr, Cm, nullptr, nullptr, nullptr, nullptr, 1, M, N, K, lda, ldb, ldc, 0, 0, 1, 0,
+                          (hipStream_t)stream, B1 - (size_t)ksplit * ldb, ksplit, 0, nullptr, false, true);
+}
+SED_API int sed_gemm_kcat_splitk_bf16x1(const float* A, const float* B0, const float* B1, float* Cm, int M, int N, int K, int ksplit,
+                                        int lda, int ldb, int ldc, int split_k, float* scratch, void* stream) {
+    if (ksplit % 32 != 0 || ksplit <= 0 || ksplit >= K) return SED_ERR_ARG;
+    if (M <= 0 || N <= 0) return SED_OK;
+    if (!scratch || N % 4 != 0 || ldc % 4 != 0) return SED_ERR_ARG;
+    if (((uintptr_t)Cm & 15) != 0) return SED_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = gemmb_dispatch(A, B0, nullptr, Cm, nullptr, nullptr, nullptr, nullptr, 1, M, N, K, lda, ldb, ldc, 0, 0, split_k, 0, s,
+                                  B1 - (size_t)ksplit * ldb, ksplit, 0, scratch, false, true);
     if (rc != SED_OK) return rc;
     SED_LAUNCH(splitk_reduce_kernel, dim3((M * N / 4 + 255) / 256, 1), dim3(256), 0, s, (const float*)scratch, Cm, Cm,
                splitk_slices(K, split_k), M, N, ldc);

@@ -834,6 +834,9 @@ def main(argv=None, cpu_test_device=False, entry_module="desed_task_amd.launcher
     if rank == 0:
         clip = config["training"].get("gradient_clip") or 0
         print("gradient_clip: %s" % ("%g (norm of the averaged gradient, clipped inside the fused Adam step)" % clip if clip > 0 else "off"))
+        print("precision: training.precision = %r -> conv_precision %s, gemm_precision %s" % (
+            config["training"].get("precision", 32), task.sed_student.cnn.conv_precision, task.sed_student.gemm_precision or
+            os.environ.get("SED_GEMM_PRECISION", "bf16x3")))
     start, best = 0, None
     if args.resume_from_checkpoint:
         ckpt = load_checkpoint(task, args.resume_from_checkpoint, resume=True)

@@ -35,10 +35,11 @@ class CNN(nn.Module):
         super().__init__()
         self.nb_filters = nb_filters
         # arithmetic of the 3x3 convolutions of blocks 1..: "f32" = exact-f32 MFMA, "bf16x3" = split-bf16 MFMA
-        # (three bf16 MFMAs per product, fp32-level accuracy; see csrc/sed_conv_bf16.hip)
+        # (three bf16 MFMAs per product, fp32-level accuracy; see csrc/sed_conv_bf16.hip), "bf16" = operands rounded once to
+        # bf16, one MFMA per product (the recipes' `training.precision: bf16`; block 0 and the GLU gate linears keep their arithmetic)
         self.conv_precision = os.environ.get("SED_CONV_PRECISION", transformer_kwargs.get("conv_precision", "bf16x3"))
-        if self.conv_precision not in ("f32", "bf16x3"):
-            raise ValueError("conv_precision must be 'f32' or 'bf16x3'")
+        if self.conv_precision not in ("f32", "bf16x3", "bf16"):
+            raise ValueError("conv_precision must be 'f32', 'bf16x3' or 'bf16'")
         self.n_in_channel = n_in_channel
         self.conv_dropout = conv_dropout
         self.pooling = [tuple(p) for p in pooling]
@@ -84,8 +85,8 @@ class CNN(nn.Module):
     FUSE_PROLOGUE = True                # bench.py --no-cnn-prologue (A/B): separate bounds / pack launches + x.clone()
 
     def can_fuse_prologue(self, x):
-        """The one-launch prologue (ops.pack_conv_weights(prologue=...)) exists for the split-bf16 packs of a CNN with >= 2 blocks."""
-        return (CNN.FUSE_PROLOGUE and self.conv_precision == "bf16x3" and len(self.nb_filters) > 1 and x.is_contiguous()
+        """The one-launch prologue (ops.pack_conv_weights(prologue=...)) exists for the split-bf16 / bf16 packs of a CNN with >= 2 blocks."""
+        return (CNN.FUSE_PROLOGUE and self.conv_precision in ("bf16x3", "bf16") and len(self.nb_filters) > 1 and x.is_contiguous()
                 and x.dtype == torch.float32 and x.data_ptr() % 16 == 0)       # (the copy moves 16-byte words)
 
     def forward(self, x, bounds=None, arena=None, specaug=None, private_input=False):

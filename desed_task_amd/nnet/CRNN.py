@@ -37,7 +37,8 @@ class CRNN(nn.Module):
                  rnn_type="BGRU", n_RNN_cell=128, n_layers_RNN=2, dropout_recurrent=0, cnn_integration=False,
                  freeze_bn=False, use_embeddings=False, embedding_size=527, embedding_type="global",
                  frame_emb_enc_dim=512, aggregation_type="global", specaugm_t_p=0.2, specaugm_t_l=5, specaugm_f_p=0.2,
-                 specaugm_f_l=10, dropstep_recurrent=0.0, dropstep_recurrent_len=5, specaugm_iid_masks=True, **kwargs):
+                 specaugm_f_l=10, dropstep_recurrent=0.0, dropstep_recurrent_len=5, specaugm_iid_masks=True, gemm_precision=None,
+                 **kwargs):
         super().__init__()
         if cnn_integration:
             raise NotImplementedError("cnn_integration is not built (SURVEY 8f)")
@@ -70,7 +71,7 @@ class CRNN(nn.Module):
             for p in self.cnn.parameters():
                 p.requires_grad = False
         self.rnn = BidirectionalGRU(n_in=self.cnn.nb_filters[-1], n_hidden=n_RNN_cell, dropout=dropout_recurrent,
-                                    num_layers=n_layers_RNN)
+                                    num_layers=n_layers_RNN, gemm_precision=gemm_precision)
         self.dropout = nn.Dropout(dropout)
         self.dense = nn.Linear(n_RNN_cell * 2, nclass)
         self.sigmoid = nn.Sigmoid()
@@ -122,6 +123,26 @@ class CRNN(nn.Module):
         new._cnn_boundary = None
         new._build_arena()
         return new
+
+    # ---- arithmetic mode ------------------------------------------------------------------------
+    @property
+    def gemm_precision(self):
+        """Mode of the tail's K7 GEMMs (BiGRU input projections and gradients, cat_tf): None = SED_GEMM_PRECISION or "bf16x3"."""
+        return self.rnn.gemm_precision
+
+    def set_precision(self, mode):
+        """One switch for both contraction families: the 3x3 convolutions of blocks 1.. (cnn.conv_precision) and the tail's GEMMs
+        (gemm_precision) run in `mode` -- "f32", "bf16x3" or "bf16" (ops.PRECISIONS).  SED_CONV_PRECISION / SED_GEMM_PRECISION, when
+        set, keep their say over their family.  The mode only selects kernels: parameters, arena views and state-dict keys are untouched."""
+        import os
+        if mode not in _ops.PRECISIONS:
+            raise ValueError("precision mode must be one of %s" % (_ops.PRECISIONS,))
+        self.cnn.conv_precision = os.environ.get("SED_CONV_PRECISION") or mode
+        self.rnn.gemm_precision = os.environ.get("SED_GEMM_PRECISION") or mode
+        for p in (self.cnn.conv_precision, self.rnn.gemm_precision):
+            if p not in _ops.PRECISIONS:
+                raise ValueError("SED_CONV_PRECISION / SED_GEMM_PRECISION must be one of %s" % (_ops.PRECISIONS,))
+        return self
 
     # ---- reference surface ----------------------------------------------------------------------
     def apply_specaugment(self, x):
@@ -182,7 +203,7 @@ class CRNN(nn.Module):
                 tmask = torch.cat((bx, be), 1).contiguous() if bx is not None else None
             drop = self.dropout.training and self.dropout_p > 0
             cfg = dict(dropout_p=self.dropout_p, apply_dropout=drop, seed=new_seed() if drop else 0, arena=arena, tmask=tmask,
-                       mode=1 if self.aggregation_type == "interpolate" else 0)
+                       mode=1 if self.aggregation_type == "interpolate" else 0, gemm_precision=self.rnn.gemm_precision)
             h = EmbCatFn.apply(h, embeddings, self.cat_tf.weight, self.cat_tf.bias, cfg)
         elif embeddings is not None:
             raise ValueError("embeddings given to a CRNN built with use_embeddings=False")

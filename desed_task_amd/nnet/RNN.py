@@ -8,8 +8,13 @@ from ..ops import BiGRULayerFn
 
 
 class BidirectionalGRU(nn.Module):
-    def __init__(self, n_in, n_hidden, dropout=0, num_layers=1):
+    def __init__(self, n_in, n_hidden, dropout=0, num_layers=1, gemm_precision=None):
         super().__init__()
+        # arithmetic of the input projections and their gradients (ops.gemm_entry): None = SED_GEMM_PRECISION or "bf16x3"; the
+        # recurrence and the gate math are fp32 in every mode
+        if gemm_precision is not None and gemm_precision not in _ops.PRECISIONS:
+            raise ValueError("gemm_precision must be 'bf16x3', 'bf16' or 'f32'")
+        self.gemm_precision = gemm_precision
         if n_hidden == 256 and not _ops.GRU_WIDE:
             raise NotImplementedError("n_hidden = 256 runs on the streamed-weight GRU kernels and is opt-in: set SED_GRU_WIDE=1 (or "
                                       "desed_task_amd.ops.GRU_WIDE = True) before building the model; 128 and 192 need no switch")
@@ -23,7 +28,7 @@ class BidirectionalGRU(nn.Module):
 
     def forward(self, input_feat, arena=None):
         x = input_feat
-        cfg = dict(arena=arena)
+        cfg = dict(arena=arena, gemm_precision=self.gemm_precision)
         for k in range(self.num_layers):
             g = lambda n: getattr(self.rnn, "%s_l%d" % (n, k))          # noqa: E731
             r = lambda n: getattr(self.rnn, "%s_l%d_reverse" % (n, k))  # noqa: E731

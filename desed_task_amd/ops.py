@@ -132,14 +132,47 @@ def flush_deferred(side):
             launch(_lib.stream_ptr(keep[0]))
 
 
+# Arithmetic modes of the contractions: "f32" = exact-f32 MFMA, "bf16x3" = three bf16 MFMAs per product on hi / lo planes (fp32-level
+# accuracy, the default), "bf16" = both operands rounded once to bf16, ONE MFMA per product, fp32 accumulation (what the recipes'
+# `training.precision: bf16` selects; DESIGN.md, "Mixed-precision mode").  The mode only picks C-ABI entries: everything in HBM stays fp32.
+PRECISIONS = ("f32", "bf16x3", "bf16")
+_SUFFIX = {"f32": "", "bf16x3": "_bf16x3", "bf16": "_bf16x1"}
+
+
+def gemm_suffix(cfg):
+    """Suffix of the K7 GEMM entries for cfg["gemm_precision"] (or SED_GEMM_PRECISION, or the default "bf16x3")."""
+    prec = (cfg or {}).get("gemm_precision") or os.environ.get("SED_GEMM_PRECISION", "bf16x3")
+    if prec not in PRECISIONS:
+        raise ValueError("gemm_precision must be 'bf16x3', 'bf16' or 'f32'")
+    return _SUFFIX[prec]
+
+
 def gemm_entry(cfg, pair=True):
     """C-ABI entry of the GRU GEMMs: split-bf16 products by default (fp32-level accuracy, see sed_gemm_bf16.hip),
-    exact-f32 MFMA with cfg["gemm_precision"] = "f32" or SED_GEMM_PRECISION=f32."""
-    prec = (cfg or {}).get("gemm_precision") or os.environ.get("SED_GEMM_PRECISION", "bf16x3")
-    if prec not in ("bf16x3", "f32"):
-        raise ValueError("gemm_precision must be 'bf16x3' or 'f32'")
-    name = "sed_gemm_pair" if pair else "sed_gemm"
-    return name + "_bf16x3" if prec == "bf16x3" else name
+    exact-f32 MFMA with cfg["gemm_precision"] = "f32" or SED_GEMM_PRECISION=f32, single-product bf16 with "bf16"."""
+    return ("sed_gemm_pair" if pair else "sed_gemm") + gemm_suffix(cfg)
+
+
+def precision_mode(value):
+    """`training.precision` of a recipe YAML (handed to the Lightning trainer by train_sed.py:279 / train_pretrained.py:453) -> the
+    arithmetic mode it selects here, or None for "leave the models as they were built".
+    32, "32", "32-true": None.  "bf16", "bf16-mixed": "bf16".  16, "16", "16-mixed", 64 and anything else: None as before, plus one
+    warning that names the modes that exist (there is no fp16 or fp64 path; raising would break recipes that ran until now)."""
+    v = str(value).strip().lower()
+    if v in ("32", "32-true"):
+        return None
+    if v in ("bf16", "bf16-mixed"):
+        return "bf16"
+    import warnings
+    warnings.warn("training.precision = %r has no counterpart on the HIP kernels and is ignored: the arithmetic modes are 32 / '32-true' "
+                  "(split-bf16 MFMA at fp32-level accuracy, the default) and 'bf16' / 'bf16-mixed' (single-product bf16 MFMA, fp32 "
+                  "accumulation, fp32 weights and activations)" % (value,), stacklevel=3)
+    return None
+
+
+def _mfma_bf16(precision):
+    """Does this conv_precision run the 3x3 convolutions on the bf16 MFMA (packed slabs, BN-fold, split-bf16 GLU gate linears)?"""
+    return precision in ("bf16x3", "bf16")
 
 
 def _p(t):
@@ -259,8 +292,9 @@ def _grad_buf(cfg, param):
 
 def pack_conv_weights(weights, need_dgrad=True, precision="f32", prologue=None):
     """Repack a list of nn.Conv2d weights (COUT,CIN,3,3) into the conv kernels' layouts, ALL layers in ONE launch.
-    precision "f32": K-major fp32 (sed_conv3x3); "bf16x3": split-bf16 slabs (sed_conv3x3_bf16x3).
-    prologue (bf16x3 only): {"bounds": seeded SpecAugment draw, "copy": (src, dst)} done by the SAME launch (sed_cnn_prologue_bf16).
+    precision "f32": K-major fp32 (sed_conv3x3); "bf16x3": split-bf16 slabs (sed_conv3x3_bf16x3); "bf16": the hi plane of those slabs
+    alone (sed_conv3x3_bf16x1).
+    prologue (bf16x3 / bf16 only): {"bounds": seeded SpecAugment draw, "copy": (src, dst)} done by the SAME launch (sed_cnn_prologue_bf16*).
     -> [(Wf, Wd or None), ...] (views into one buffer; Wd = flipped/transposed pack for the data gradient)."""
     import ctypes
     n = len(weights)
@@ -283,19 +317,19 @@ def pack_conv_weights(weights, need_dgrad=True, precision="f32", prologue=None):
         W[k] = w.data_ptr(); Wf[k] = wf.data_ptr(); Wd[k] = wd.data_ptr() if wd is not None else None
         co[k] = w.shape[0]; ci[k] = w.shape[1]
     if prologue is not None:
-        if precision != "bf16x3":
-            raise ValueError("the fused CNN prologue is built for the split-bf16 packs")
+        if not _mfma_bf16(precision):
+            raise ValueError("the fused CNN prologue is built for the split-bf16 and bf16 packs")
         b = prologue.get("bounds")                         # dict(out, n, f_param, n_freq, t_param, n_time, seed) or None
         c = prologue.get("copy")                           # (src, dst) or None
         seed = b["seed"] if b else 0
-        _lib.get().call("sed_cnn_prologue_bf16", n, W, Wf, Wd, co, ci,
+        _lib.get().call("sed_cnn_prologue_bf16x1" if precision == "bf16" else "sed_cnn_prologue_bf16", n, W, Wf, Wd, co, ci,
                         b["out"].data_ptr() if b else None, b["out"].shape[0] if b else 0, b["n"] if b else 1,
                         b["f_param"] if b else 0, b["n_freq"] if b else 1, b["t_param"] if b else 0, b["n_time"] if b else 1,
                         int(seed) & 0xFFFFFFFF, getattr(seed, "dev", None),
                         c[0].data_ptr() if c else None, c[1].data_ptr() if c else None, c[0].numel() if c else 0,
                         _lib.stream_ptr(buf))
         return out
-    entry = "sed_conv_pack_multi_bf16" if precision == "bf16x3" else "sed_conv_pack_multi"
+    entry = {"bf16x3": "sed_conv_pack_multi_bf16", "bf16": "sed_conv_pack_multi_bf16x1"}.get(precision, "sed_conv_pack_multi")
     _lib.get().call(entry, n, W, Wf, Wd, co, ci, _lib.stream_ptr(buf))
     return out
 
@@ -350,7 +384,9 @@ class ConvBlockFn(torch.autograd.Function):
             return out
         ctx.fused0 = False
         y = torch.empty(B, T, F, COUT, device=dev, dtype=torch.float32)
-        bf16x3 = (not first) and cfg.get("conv_precision", "f32") == "bf16x3" and cfg.get("packed") is not None
+        prec = cfg.get("conv_precision", "f32")
+        bf16x3 = (not first) and _mfma_bf16(prec) and cfg.get("packed") is not None
+        sfx = _SUFFIX[prec] if bf16x3 else ""         # "_bf16x3" / "_bf16x1": the same tiling, so the same `partial` layout
         nblk = lib.value("sed_conv_fwd_blocks_bf16" if bf16x3 else "sed_conv_fwd_blocks", B, T, F, CIN, COUT)
         partial = torch.empty(nblk * 2 * COUT, device=dev, dtype=torch.float32) if training else None
         conv_w = conv_w.contiguous()
@@ -364,7 +400,7 @@ class ConvBlockFn(torch.autograd.Function):
             else:
                 wf = torch.empty(9 * CIN * COUT, device=dev, dtype=torch.float32)
                 lib.call("sed_conv_pack_weights", conv_w.data_ptr(), wf.data_ptr(), None, COUT, CIN, st)
-            lib.call("sed_conv3x3_bf16x3" if bf16x3 else "sed_conv3x3", x.data_ptr(), wf.data_ptr(), _p(conv_b), y.data_ptr(), _p(partial), B, T, F, CIN, COUT, st)
+            lib.call("sed_conv3x3" + sfx, x.data_ptr(), wf.data_ptr(), _p(conv_b), y.data_ptr(), _p(partial), B, T, F, CIN, COUT, st)
         stats = torch.empty(4 * COUT, device=dev, dtype=torch.float32)
         lib.call("sed_bn_finalize", _p(partial), nblk, COUT, float(B * T * F), bn_w.data_ptr(), bn_b.data_ptr(),
                  running_mean.data_ptr(), running_var.data_ptr(), BN_MOMENTUM, BN_EPS, stats.data_ptr(), int(training),
@@ -372,7 +408,7 @@ class ConvBlockFn(torch.autograd.Function):
         out = torch.empty(B, T // PT, F // PF, COUT, device=dev, dtype=torch.float32)
         glu_w = glu_w.contiguous()
         lib.call("sed_glu_fwd", y.data_ptr(), stats.data_ptr(), glu_w.data_ptr(), glu_b.data_ptr(), out.data_ptr(), B, T, F, COUT,
-                 PT, PF, int(seed), thr24, dscale, _graph.seed_dev(seed), int(cfg.get("conv_precision", "f32") == "bf16x3"), st)
+                 PT, PF, int(seed), thr24, dscale, _graph.seed_dev(seed), int(_mfma_bf16(prec)), st)
         ctx.save_for_backward(x, y, stats, conv_w, bn_w, bn_b, glu_w, glu_b, conv_b)
         ctx.meta = (first, B, T, F, CIN, COUT, PT, PF, training, seed, thr24, dscale, bounds)
         ctx.cfg = cfg
@@ -416,7 +452,7 @@ class ConvBlockFn(torch.autograd.Function):
         lib.call("sed_glu_bwd", y.data_ptr(), stats.data_ptr(), bn_w.data_ptr(), bn_b.data_ptr(), glu_w.data_ptr(), glu_b.data_ptr(),
                  gout.data_ptr(), dz.data_ptr(), d_glu_w.data_ptr(), d_glu_b.data_ptr(), d_gamma.data_ptr(), d_beta.data_ptr(),
                  _p(gscratch), B, T, F, COUT, PT, PF, int(seed), thr24, dscale, _graph.seed_dev(seed),
-                 int(cfg.get("conv_precision", "f32") == "bf16x3"), st)
+                 int(_mfma_bf16(cfg.get("conv_precision", "f32"))), st)
         if _deferred:           # the last BiGRU layer's side section: enqueued now that the chain's next kernel is
             flush_deferred(side_stream(dev) if GRU_DW_SIDE else None)
         d_bias = _grad_buf(cfg, conv_b)
@@ -428,19 +464,21 @@ class ConvBlockFn(torch.autograd.Function):
                      d_gamma.data_ptr(), d_beta.data_ptr(), d_w.data_ptr(), d_bias.data_ptr(), B, T, F, COUT, 1, 1, st)
             return dx, d_w, d_bias, d_gamma, d_beta, d_glu_w, d_glu_b, None, None, None
         packed = cfg.get("packed")
-        if (BN_BWD_FOLD and training and not first and ctx.needs_input_grad[0] and cfg.get("conv_precision", "f32") == "bf16x3"
+        prec = cfg.get("conv_precision", "f32")
+        sfx = _SUFFIX[prec]
+        if (BN_BWD_FOLD and training and not first and ctx.needs_input_grad[0] and _mfma_bf16(prec)
                 and packed is not None and packed[1] is not None):
             # data gradient first: it forms dy = BN-backward(dz) while staging its operand and leaves dy behind for the weight
             # gradient (bit-identical to the separate sed_bn_bwd_apply pass: same expression, operation for operation)
             dy = torch.empty_like(dz)
             dx = torch.empty_like(x)
-            lib.call("sed_conv3x3_bf16x3_bnbwd", dz.data_ptr(), y.data_ptr(), stats.data_ptr(), bn_w.data_ptr(), d_gamma.data_ptr(),
+            lib.call("sed_conv3x3%s_bnbwd" % sfx, dz.data_ptr(), y.data_ptr(), stats.data_ptr(), bn_w.data_ptr(), d_gamma.data_ptr(),
                      d_beta.data_ptr(), packed[1].data_ptr(), dx.data_ptr(), dy.data_ptr(), d_bias.data_ptr(), B, T, F, COUT, CIN, st)
             scratch = torch.empty(int(lib.value("sed_conv_wgrad_scratch_floats", B, T, F, CIN, COUT)), **f32)
             d_w_ptr = d_w.data_ptr()            # (an address, not the tensor, goes into what outlives this call: see defer_off_chain)
 
             def wgrad(stream_ptr):
-                lib.call("sed_conv_wgrad_bf16x3", x.data_ptr(), dy.data_ptr(), scratch.data_ptr(), d_w_ptr, B, T, F, CIN, COUT, stream_ptr)
+                lib.call("sed_conv_wgrad" + sfx, x.data_ptr(), dy.data_ptr(), scratch.data_ptr(), d_w_ptr, B, T, F, CIN, COUT, stream_ptr)
             if CNN_DW_SIDE and CNN_DW_SIDE_NOW and _arena_views(cfg, d_w):
                 # the chain goes on with the block below (its GLU backward reads dx); dW only feeds the optimizer.  Parked until that
                 # block's first kernel is enqueued, then launched on the side stream beside it (block 1's goes out beside block 0's
@@ -457,20 +495,19 @@ class ConvBlockFn(torch.autograd.Function):
                      B, T, F, COUT, 0, int(training), st)
         else:
             scratch = torch.empty(int(lib.value("sed_conv_wgrad_scratch_floats", B, T, F, CIN, COUT)), **f32)
-            entry = "sed_conv_wgrad_bf16x3" if cfg.get("conv_precision", "f32") == "bf16x3" else "sed_conv_wgrad"
-            lib.call(entry, x.data_ptr(), dy.data_ptr(), scratch.data_ptr(), d_w.data_ptr(), B, T, F, CIN, COUT, st)
+            lib.call("sed_conv_wgrad" + sfx, x.data_ptr(), dy.data_ptr(), scratch.data_ptr(), d_w.data_ptr(), B, T, F, CIN, COUT, st)
             if ctx.needs_input_grad[0]:
                 packed = cfg.get("packed")
                 bf16x3 = False
                 if packed is not None and packed[1] is not None:
                     wd = packed[1]                # packed with the forward weights (same values: no optimizer step in between)
-                    bf16x3 = cfg.get("conv_precision", "f32") == "bf16x3"
+                    bf16x3 = _mfma_bf16(prec)
                 else:
                     wd = torch.empty(9 * CIN * COUT, **f32)
                     wf = torch.empty(9 * CIN * COUT, **f32)
                     lib.call("sed_conv_pack_weights", conv_w.data_ptr(), wf.data_ptr(), wd.data_ptr(), COUT, CIN, st)
                 dx = torch.empty_like(x)
-                lib.call("sed_conv3x3_bf16x3" if bf16x3 else "sed_conv3x3", dy.data_ptr(), wd.data_ptr(), None, dx.data_ptr(), None, B, T, F, COUT, CIN, st)
+                lib.call("sed_conv3x3" + (sfx if bf16x3 else ""), dy.data_ptr(), wd.data_ptr(), None, dx.data_ptr(), None, B, T, F, COUT, CIN, st)
         return dx, d_w, d_bias, d_gamma, d_beta, d_glu_w, d_glu_b, None, None, None
 
 
@@ -546,13 +583,14 @@ class BiGRULayerFn(torch.autograd.Function):
             # side by side, so this is ONE product over K = 6H whose B operand switches tensors at k = 3H (no atomics, no
             # zero fill)
             dx = torch.empty(B, T, I, **f32)
-            kcat = "sed_gemm_kcat_bf16x3" if gemm_entry(cfg).endswith("bf16x3") else "sed_gemm_kcat"
+            gsfx = gemm_suffix(cfg)
+            kcat = "sed_gemm_kcat" + gsfx
             # one slice is (I / 64) x (B T / 128) workgroups walking 6 H / 32 dependent K tiles with the chip half empty: aim at ~ 700
             # workgroups (three resident per CU), slices of at least four tiles
             nsl = min(max(1, round(700.0 / (((I + 63) // 64) * ((BT + 127) // 128)))), max(1, (6 * H) // 128)) if GRU_DX_SPLITK else 1
-            if kcat.endswith("bf16x3") and nsl > 1 and I % 4 == 0 and dx.data_ptr() % 16 == 0:
+            if gsfx and nsl > 1 and I % 4 == 0 and dx.data_ptr() % 16 == 0:
                 scr = torch.empty(int(lib.value("sed_gemm_splitk_scratch_floats", BT, I, 6 * H, nsl)) // 2, **f32)
-                lib.call("sed_gemm_kcat_splitk_bf16x3", dgi.data_ptr(), w_ih_f.data_ptr(), w_ih_r.data_ptr(), dx.data_ptr(), BT, I, 6 * H,
+                lib.call("sed_gemm_kcat_splitk" + gsfx, dgi.data_ptr(), w_ih_f.data_ptr(), w_ih_r.data_ptr(), dx.data_ptr(), BT, I, 6 * H,
                          3 * H, 6 * H, I, I, nsl, scr.data_ptr(), st)
             else:
                 lib.call(kcat, dgi.data_ptr(), w_ih_f.data_ptr(), w_ih_r.data_ptr(), dx.data_ptr(), BT, I, 6 * H, 3 * H, 6 * H, I, I, st)
@@ -590,14 +628,15 @@ class BiGRULayerFn(torch.autograd.Function):
         """wptr = ([&dW_ih fwd, rev], [&dW_hh fwd, rev], their element counts x 2): the outputs by address (see defer_off_chain)."""
         dwi, dwh, ni, nh = wptr
         BT, off = B * T, 3 * H * 4
-        if (gemm_entry(cfg).endswith("bf16x3") and I % 4 == 0 and H % 4 == 0 and all(a % 16 == 0 for a in dwi + dwh)
+        gsfx = gemm_suffix(cfg)
+        if (gsfx and I % 4 == 0 and H % 4 == 0 and all(a % 16 == 0 for a in dwi + dwh)
                 and not (cfg or {}).get("gru_dw_atomic", GRU_DW_ATOMIC)):
             # deterministic split-K: dense per-slice partials + a fixed-order sum (no zero fill, no fp32 atomics: 5 M atomics on
             # 98 K addresses were most of these launches)
             scr = torch.empty(int(lib.value("sed_gemm_splitk_scratch_floats", 3 * H, max(I, H), BT, split)), **f32)
-            lib.call("sed_gemm_pair_splitk_bf16x3", dgi.data_ptr(), dgi.data_ptr() + off, x.data_ptr(), x.data_ptr(),
+            lib.call("sed_gemm_pair_splitk" + gsfx, dgi.data_ptr(), dgi.data_ptr() + off, x.data_ptr(), x.data_ptr(),
                      dwi[0], dwi[1], 3 * H, I, BT, 6 * H, I, I, 1, 0, split, scr.data_ptr(), ws)
-            lib.call("sed_gemm_pair_splitk_bf16x3", dgh.data_ptr(), dgh.data_ptr() + off, hprev.data_ptr(), hprev.data_ptr() + H * 4,
+            lib.call("sed_gemm_pair_splitk" + gsfx, dgh.data_ptr(), dgh.data_ptr() + off, hprev.data_ptr(), hprev.data_ptr() + H * 4,
                      dwh[0], dwh[1], 3 * H, H, BT, 6 * H, 2 * H, H, 1, 0, split, scr.data_ptr(), ws)
         else:
             lib.call("sed_zero_buffers", dwi[0], ni[0], dwi[1], ni[1],
@@ -661,10 +700,10 @@ class EmbCatFn(torch.autograd.Function):
                      _p(ctx.tmask), T, st)
         dw, db = _grad_buf(cfg, w), _grad_buf(cfg, b)
         split = max(1, min(32, M // 256))
-        if entry.endswith("bf16x3") and W % 4 == 0 and dw.data_ptr() % 16 == 0:
+        if gemm_suffix(cfg) and W % 4 == 0 and dw.data_ptr() % 16 == 0:
             # deterministic split-K (dense per-slice partials + a fixed-order sum): no zero fill, no float atomics
             scr = torch.empty(int(lib.value("sed_gemm_splitk_scratch_floats", C, W, M, split)), device=dy.device, dtype=torch.float32)
-            lib.call("sed_gemm_splitk_bf16x3", dy.data_ptr(), z.data_ptr(), dw.data_ptr(), C, W, M, C, W, W, 1, 0, split, scr.data_ptr(), st)
+            lib.call("sed_gemm_splitk" + gemm_suffix(cfg), dy.data_ptr(), z.data_ptr(), dw.data_ptr(), C, W, M, C, W, W, 1, 0, split, scr.data_ptr(), st)
         else:
             lib.call("sed_zero_buffers", dw.data_ptr(), dw.numel(), None, 0, None, 0, None, 0, st)             # split-K accumulates
             lib.call(entry, dy.data_ptr(), z.data_ptr(), None, dw.data_ptr(), C, W, M, C, W, W, 1, 0, split, 0, st)  # dy^T . z

@@ -69,6 +69,13 @@ class SEDTask4(_Base):
 
         for p in self.sed_teacher.parameters():
             p.detach_()
+        # `training.precision` (train_sed.py:279 hands it to the trainer): "bf16" / "bf16-mixed" put the student AND the teacher into
+        # the single-product bf16 mode, for training, validation and test alike (as autocast would); 32 changes nothing.  A by-value
+        # choice of kernels: nothing in capture / replay, the arena or the state dict depends on it.
+        self.precision_mode = _ops.precision_mode(self.hparams["training"].get("precision", 32))
+        if self.precision_mode is not None:
+            for net in (self.sed_student, self.sed_teacher):
+                net.set_precision(self.precision_mode)
 
         sup = self.hparams["training"]["self_sup_loss"]
         if sup not in ("mse", "bce"):                       # sed_trainer.py:97-103

@@ -133,6 +133,26 @@ int sed_conv3x3_bf16x3_bnbwd(const float* dz, const float* ybn, const float* sta
                              int CIN, int COUT, void* stream);
 int sed_conv_fwd_blocks_bf16(int B, int T, int F, int CIN, int COUT);   /* rows of `partial` for the bf16x3 forward */
 
+/* Single-product ("bf16x1") twins of the four entries above -- the "bf16" arithmetic mode, what `training.precision: bf16` selects
+ * (train_sed.py:279 / train_pretrained.py:453 hand the key to the trainer; there it is autocast around CNN.py:69-72).  Both operands of
+ * the contraction are rounded ONCE to bf16 (round to nearest even), one v_mfma_f32_32x32x16_bf16 per product, fp32 accumulation; bias,
+ * BatchNorm statistics, inputs and outputs stay fp32.  The packs hold the hi plane only (first half of the same buffers) and the
+ * kernels keep no lo plane in LDS.  Same tiling and k order as the bf16x3 entries (`partial` rows: sed_conv_fwd_blocks_bf16), so on
+ * operands that are bf16 values already an entry and its twin return the same bits.  sed_conv3x3_bf16x1_bnbwd rounds the dy it forms
+ * once for the MFMA; the fp32 dy_out it writes is bit-identical to sed_conv3x3_bf16x3_bnbwd's. */
+int sed_conv_pack_multi_bf16x1(int n, const void* const* W, void* const* Wf, void* const* Wd, const int* cout,
+                               const int* cin, void* stream);
+int sed_conv3x3_bf16x1(const float* x, const void* Wp, const float* bias, float* y, float* partial, int B, int T, int F,
+                       int CIN, int COUT, void* stream);
+/* CRNN.py:207-232 as sed_cnn_prologue_bf16, with the packs of sed_conv_pack_multi_bf16x1. */
+int sed_cnn_prologue_bf16x1(int n, const void* const* W, void* const* Wf, void* const* Wd, const int* cout, const int* cin,
+                            int* bounds, int B, int nb, int f_param, int n_freq, int t_param, int n_time, unsigned seed,
+                            const unsigned* seed_dev, const float* copy_src, float* copy_dst, long long copy_n, void* stream);
+/* CNN.py:69-76 backward as sed_conv3x3_bf16x3_bnbwd. */
+int sed_conv3x3_bf16x1_bnbwd(const float* dz, const float* ybn, const float* stats, const float* gamma, const float* dgamma,
+                             const float* dbeta, const void* Wd, float* dx, float* dy_out, float* dbias, int B, int T, int F,
+                             int CIN, int COUT, void* stream);
+
 /* Layer 0 (CIN=1): direct conv with the SpecAugment predicate (CRNN.py:207-219) fused into the load.
  * x (B,T,F) scaled log-mel; W (16,1,3,3) PyTorch layout; bounds (B,4) int32 [f0,f1,t0,t1) or null.  y may be null: only the
  * BatchNorm partial statistics are produced (first pass of the fused first block below). */
@@ -197,6 +217,10 @@ int sed_conv_wgrad(const float* x, const float* dy, float* dWp, float* dW, int B
  * bf16 MFMAs per product, fp32 accumulate: ~8e-6 relative). */
 int sed_conv_wgrad_bf16x3(const float* x, const float* dy, float* dWp, float* dW, int B, int T, int F, int CIN, int COUT,
                           void* stream);
+/* Its single-product twin (the "bf16" mode; CNN.py:69-72 backward under `training.precision: bf16`): x and dy rounded once to bf16,
+ * one MFMA per product, fp32 accumulation, the same kernels' tiling, scratch and fixed-order reduce. */
+int sed_conv_wgrad_bf16x1(const float* x, const float* dy, float* dWp, float* dW, int B, int T, int F, int CIN, int COUT,
+                          void* stream);
 
 /* Layer-0 weight gradient: x (B,T,F) (+ SpecAugment bounds or null) -> dW (16,1,3,3).  fuse_bn = 0: dyz = dy (B,T,F,16).
  * fuse_bn = 1 (training mode): dyz = dz from sed_glu_bwd and the BatchNorm backward (sed_bn_bwd_apply) is applied while
@@ -244,6 +268,26 @@ int sed_gemm_pair_splitk_bf16x3(const float* A0, const float* A1, const float* B
 /* One product with the same deterministic split-K (`cat_tf` weight gradient of the embedding recipes, CRNN.py:283-296 backward:
  * dW = dy^T . [x | emb] over K = B T rows).  scratch: sed_gemm_splitk_scratch_floats(M, N, K, split_k) floats. */
 int sed_gemm_splitk_bf16x3(const float* A, const float* Bm, float* Cm, int M, int N, int K, int lda, int ldb, int ldc,
+                           int transA, int transB, int split_k, float* scratch, void* stream);
+
+/* Single-product ("bf16x1") twins of the six split-bf16 GEMM entries -- the "bf16" mode of the BiGRU input projections and their
+ * gradients (RNN.py:19-30: dX, dW_ih and the recurrent dW_hh = dgh^T h_prev) and of cat_tf (CRNN.py:283-296) under `training.precision: bf16` (train_sed.py:279,
+ * train_pretrained.py:453): A and B rounded once to bf16, one MFMA per product, fp32 accumulation, bias and outputs fp32.  Same
+ * contracts, tiles, K slices, scratch and reduce order as the entries they are named after (and the same exact-f32 fall-back / refusal
+ * for operands that miss the 16-byte requirements); bit-identical to them on operands that are bf16 values already. */
+int sed_gemm_bf16x1(const float* A, const float* Bm, const float* bias, float* Cm, int M, int N, int K, int lda, int ldb,
+                    int ldc, int transA, int transB, int split_k, int accumulate, void* stream);
+int sed_gemm_pair_bf16x1(const float* A0, const float* A1, const float* B0, const float* B1, const float* bias0,
+                         const float* bias1, float* C0, float* C1, int M, int N, int K, int lda, int ldb, int ldc,
+                         int transA, int transB, int split_k, int accumulate, void* stream);
+int sed_gemm_kcat_bf16x1(const float* A, const float* B0, const float* B1, float* Cm, int M, int N, int K, int ksplit, int lda,
+                         int ldb, int ldc, void* stream);
+int sed_gemm_kcat_splitk_bf16x1(const float* A, const float* B0, const float* B1, float* Cm, int M, int N, int K, int ksplit,
+                                int lda, int ldb, int ldc, int split_k, float* scratch, void* stream);
+int sed_gemm_pair_splitk_bf16x1(const float* A0, const float* A1, const float* B0, const float* B1, float* C0, float* C1,
+                                int M, int N, int K, int lda, int ldb, int ldc, int transA, int transB, int split_k,
+                                float* scratch, void* stream);
+int sed_gemm_splitk_bf16x1(const float* A, const float* Bm, float* Cm, int M, int N, int K, int lda, int ldb, int ldc,
                            int transA, int transB, int split_k, float* scratch, void* stream);
 
 /* Column sums (bias gradients): out[n] = sum_m X[m*ld + n] for n < nsplit, out1[n-nsplit] for nsplit <= n < N. */

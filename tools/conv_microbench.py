@@ -14,9 +14,9 @@ y = torch.empty(B, T, F, COUT, device="cuda")
 nblk = 4 * lib.value("sed_conv_fwd_blocks", B, T, F, CIN, COUT)
 partial = torch.empty(nblk * 2 * COUT, device="cuda")
 st = torch.cuda.current_stream().cuda_stream
-for mode in ("f32", "bf16x3"):
-    (wf, wd), = pack_conv_weights([w], True, "f32" if mode == "f32" else "bf16x3")
-    entry = {"f32": "sed_conv3x3", "bf16x3": "sed_conv3x3_bf16x3"}[mode]
+for mode in ("f32", "bf16x3", "bf16"):
+    (wf, wd), = pack_conv_weights([w], True, mode)
+    entry = {"f32": "sed_conv3x3", "bf16x3": "sed_conv3x3_bf16x3", "bf16": "sed_conv3x3_bf16x1"}[mode]
     def run():
         lib.call(entry, x.data_ptr(), wf.data_ptr(), bias.data_ptr(), y.data_ptr(), partial.data_ptr(), B, T, F, CIN, COUT, st)
     for _ in range(3): run()
