@@ -11,8 +11,14 @@ checkpoints load unchanged, they never run torch arithmetic.
 
 Not built: padding masks, `layer_norm_first` checkpoints, the fine-tuned predictor head, training of the extractor
 (`pretrained.e2e`) -- they raise.
+
+Arithmetic modes (`BEATs.set_precision`, `BEATsModel(..., precision=)`, environment variable SED_BEATS_PRECISION): "bf16x3" (default) = every
+product as three bf16 MFMAs on split operands, fp32-level accuracy; "bf16" = both operands of every contraction rounded once to bf16, one
+MFMA per product, fp32 accumulation (the *_bf16x1 entries; DESIGN.md "Mixed-precision mode", the extractor) -- an opt-in, ~15 x coarser
+on the embeddings.  The fbank, the LayerNorms, the gate of the relative-position bias and the bias table are fp32 in both.
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -27,6 +33,17 @@ LINEAR_TILES = True             # round 6: the q / k / v projection through the 
 LINEAR_TILES_FFN = True         # ... and fc1 -> GELU -> fc2 the same way (fc1 writes its output as fc2's image, no fp32 copy of the 3072-wide hidden state)
 LINEAR_TILES_KSPLIT = True      # ... fc2 (N = 768) as two K halves whose partial sums the final LayerNorm adds (round quantisation: 2 rounds -> 1.5)
 LINEAR_PACKED = True            # the large Linear layers through the packed-weight 256 x 128-tile kernel (False: sed_linear_bf16x3, A/B and tests)
+PRECISIONS = ("bf16x3", "bf16")  # arithmetic modes of the contractions; the switches above keep their meaning in both
+
+
+def resolve_precision(mode):
+    """None -> the environment variable SED_BEATS_PRECISION if set, else "bf16x3"; anything but the two modes raises."""
+    if mode is None:
+        mode = os.environ.get("SED_BEATS_PRECISION") or "bf16x3"
+    if mode not in PRECISIONS:
+        raise ValueError("BEATs precision %r: the extractor's modes are %r (three-product split-bf16, fp32-level) and %r (both operands "
+                         "rounded once to bf16, one MFMA per product)" % (mode, PRECISIONS[0], PRECISIONS[1]))
+    return mode
 
 
 class BEATsConfig:
@@ -188,6 +205,13 @@ class BEATs(nn.Module):
         self.fbank = KaldiFbank(128)
         self._packed = None
         self._relb = {}
+        self.precision = resolve_precision(None)
+
+    def set_precision(self, mode):
+        """"bf16x3" | "bf16" (None: SED_BEATS_PRECISION, else "bf16x3").  The derived copies (weight images, position-convolution planes,
+        activation image buffers) are keyed by the mode: nothing built for the other mode is read afterwards."""
+        self.precision = resolve_precision(mode)
+        return self
 
     # ---- frozen-weight preparation (once per load) -----------------------------------------------------------------------
     def load_state_dict(self, *a, **k):
@@ -221,13 +245,23 @@ class BEATs(nn.Module):
                 wqkv=torch.cat((a.q_proj.weight, a.k_proj.weight, a.v_proj.weight), 0).detach().float().contiguous(),
                 bqkv=torch.cat((a.q_proj.bias, a.k_proj.bias, a.v_proj.bias), 0).detach().float().contiguous(),
                 grep_a=a.grep_a.detach().float().reshape(-1).contiguous() if cfg.gru_rel_pos else None))
-        # the position convolution's B operand for the split-bf16 MFMA: hi = bf16(w), lo = bf16(w - hi), as bit patterns
-        w_hi = wt.to(torch.bfloat16)
-        w_lo = (wt - w_hi.float()).to(torch.bfloat16)
-        wsplit = torch.stack((w_hi, w_lo)).contiguous().view(torch.int16)
-        self._packed = dict(wt=wt, wsplit=wsplit, layers=layers,
+        self._packed = dict(wt=wt, layers=layers,
                             wpatch=self.patch_embedding.weight.detach().float().reshape(self.embed, -1).contiguous())
         return self._packed
+
+    def _posconv_planes(self, pk, mode):
+        """The position convolution's B operand for the MFMA kernels, as bit patterns: "bf16x3" -> hi = bf16(w), lo = bf16(w - hi) stacked;
+        "bf16" -> the hi plane alone."""
+        key = ("wpos", mode)
+        if key not in pk:
+            wt = pk["wt"]
+            w_hi = wt.to(torch.bfloat16)
+            if mode == "bf16":
+                pk[key] = w_hi.contiguous().view(torch.int16)
+            else:
+                w_lo = (wt - w_hi.float()).to(torch.bfloat16)
+                pk[key] = torch.stack((w_hi, w_lo)).contiguous().view(torch.int16)
+        return pk[key]
 
     def _rel_bias(self, T, device):
         """(H, 2T - 1): relative_attention_bias[bucket(s - t)] per offset (backbone.py:390-444)."""
@@ -261,6 +295,10 @@ class BEATs(nn.Module):
         lib = _lib.get()
         cfg = self.cfg
         pk = self._pack()
+        mode = self.precision
+        one = mode == "bf16"                  # the single-product entry family (*_bf16x1); same arguments as the three-product twins
+        sfx = "_bf16x1" if one else "_bf16x3"
+        planes = 1 if one else 2              # 16-bit words of a tile image per element
         fb = self.preprocess(source, fbank_mean, fbank_std)                       # (B, M, 128)
         st = _lib.stream_ptr(fb)
         B, M, F = fb.shape
@@ -273,6 +311,10 @@ class BEATs(nn.Module):
 
         def linear(x, w, b, n, k, act=0):
             y = torch.empty(x.shape[0], n, **f32)
+            if one:                           # (no packed-weight kernel in this mode: its shapes take the generic tile too)
+                lib.call("sed_linear_bf16x1", x.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None, y.data_ptr(),
+                         x.shape[0], n, k, act, st)
+                return y
             if LINEAR_PACKED and n >= 2048 and n % 128 == 0 and k % 32 == 0 and x.shape[0] >= 256:
                 # frozen weight: split into bf16 hi / lo planes once, then the 256 x 128-tile kernel (sed_gemm_bf16.hip, round 5).  Wide
                 # outputs only: at N = 768 its 558 tiles on 512 resident workgroups lose to the 128-row tiles (gpurun_out/linear_r05a.txt)
@@ -293,7 +335,7 @@ class BEATs(nn.Module):
         def layernorm(x, res, alpha, ln, d, image=None, x2=None):
             y = torch.empty_like(x)
             if image is not None:
-                lib.call("sed_layernorm_tiles", x.data_ptr(), x2.data_ptr() if x2 is not None else None, res.data_ptr() if res is not None else None, float(alpha), ln.weight.data_ptr(),
+                lib.call("sed_layernorm_tiles_bf16x1" if one else "sed_layernorm_tiles", x.data_ptr(), x2.data_ptr() if x2 is not None else None, res.data_ptr() if res is not None else None, float(alpha), ln.weight.data_ptr(),
                          ln.bias.data_ptr(), y.data_ptr(), image.data_ptr(), x.shape[0], d, float(ln.eps), st)
                 return y
             lib.call("sed_layernorm", x.data_ptr(), res.data_ptr() if res is not None else None, float(alpha), ln.weight.data_ptr(),
@@ -304,34 +346,34 @@ class BEATs(nn.Module):
         # it) and its frozen weight as the same kind of image (built once); ONE image buffer, re-written by every layer's last LayerNorm
         tiles = LINEAR_TILES and D % 256 == 0 and R >= 256
         # (zeros: the LayerNorm writes rows < R only; the rows of the padded last panel then stay finite all the way through fc1 -> fc2)
-        imgs = self._relb.get(("images", R, D, fb.device))                      # (kept across calls: 2 x 73 MB at 48 clips; dropped with the other caches)
+        imgs = self._relb.get(("images", mode, R, D, fb.device))                # (kept across calls: 2 x 73 MB at 48 clips, half of it in "bf16"; dropped with the other caches)
         if tiles and imgs is None:
-            imgs = self._relb[("images", R, D, fb.device)] = [torch.zeros(2 * ((R + 255) // 256) * 256 * D, device=fb.device, dtype=torch.int16) for _ in range(2)]
+            imgs = self._relb[("images", mode, R, D, fb.device)] = [torch.zeros(planes * ((R + 255) // 256) * 256 * D, device=fb.device, dtype=torch.int16) for _ in range(2)]
         ximg = imgs[0] if tiles else None
 
         Fd = cfg.encoder_ffn_embed_dim
         ffn_tiles = tiles and LINEAR_TILES_FFN and Fd % 256 == 0
         ximg2 = imgs[1] if ffn_tiles else None                      # the attention block's LayerNorm output -> fc1
-        himg = torch.empty(2 * ((R + 255) // 256) * 256 * Fd, device=fb.device, dtype=torch.int16) if ffn_tiles else None   # GELU(fc1) -> fc2
+        himg = torch.empty(planes * ((R + 255) // 256) * 256 * Fd, device=fb.device, dtype=torch.int16) if ffn_tiles else None   # GELU(fc1) -> fc2
 
         def linear_tiles(img, w, b, n, k, act=0, out_image=None, split2=False):
-            key = ("tiles", w.data_ptr(), w._version, n, k)
+            key = ("tiles", mode, w.data_ptr(), w._version, n, k)
             wt_ = packed.get(key)
             if wt_ is None or wt_.device != fb.device:
-                wt_ = torch.empty(2 * ((n + 255) // 256) * 256 * k, device=fb.device, dtype=torch.int16)
+                wt_ = torch.empty(planes * ((n + 255) // 256) * 256 * k, device=fb.device, dtype=torch.int16)
                 wsrc = w.detach().float().contiguous()
-                lib.call("sed_split_tiles_bf16x3", wsrc.data_ptr(), wt_.data_ptr(), n, k, st)
+                lib.call("sed_split_tiles" + sfx, wsrc.data_ptr(), wt_.data_ptr(), n, k, st)
                 packed[key] = wt_
             bp = b.data_ptr() if b is not None else None
             if out_image is not None:           # the product leaves as the next Linear's image (fc1's GELU output is only read by fc2)
-                lib.call("sed_linear_tiles_out_bf16x3", img.data_ptr(), wt_.data_ptr(), bp, out_image.data_ptr(), R, n, k, act, st)
+                lib.call("sed_linear_tiles_out" + sfx, img.data_ptr(), wt_.data_ptr(), bp, out_image.data_ptr(), R, n, k, act, st)
                 return None
             if split2:                           # two partial sums over the halves of K: (2, R, n)
                 y = torch.empty(2, R, n, **f32)
-                lib.call("sed_linear_tiles_split2_bf16x3", img.data_ptr(), wt_.data_ptr(), bp, y.data_ptr(), R, n, k, st)
+                lib.call("sed_linear_tiles_split2" + sfx, img.data_ptr(), wt_.data_ptr(), bp, y.data_ptr(), R, n, k, st)
                 return y
             y = torch.empty(R, n, **f32)
-            lib.call("sed_linear_tiles_bf16x3", img.data_ptr(), wt_.data_ptr(), bp, y.data_ptr(), R, n, k, act, st)
+            lib.call("sed_linear_tiles" + sfx, img.data_ptr(), wt_.data_ptr(), bp, y.data_ptr(), R, n, k, act, st)
             return y
 
         patches = torch.empty(R, P * P, **f32)
@@ -343,7 +385,7 @@ class BEATs(nn.Module):
         enc = self.encoder
         y = torch.empty_like(x)
         if POSCONV_MFMA and D // cfg.conv_pos_groups == 48 and cfg.conv_pos % 4 == 0:
-            lib.call("sed_posconv_bf16x3", x.data_ptr(), pk["wsplit"].data_ptr(), enc.pos_conv[0].bias.data_ptr(), y.data_ptr(), B, T, D,
+            lib.call("sed_posconv" + sfx, x.data_ptr(), self._posconv_planes(pk, mode).data_ptr(), enc.pos_conv[0].bias.data_ptr(), y.data_ptr(), B, T, D,
                      cfg.conv_pos, cfg.conv_pos_groups, st)
         else:
             lib.call("sed_posconv", x.data_ptr(), pk["wt"].data_ptr(), enc.pos_conv[0].bias.data_ptr(), y.data_ptr(), B, T, D, cfg.conv_pos,
@@ -358,7 +400,8 @@ class BEATs(nn.Module):
             qkv = linear_tiles(ximg, lp["wqkv"], lp["bqkv"], 3 * D, D) if tiles else linear(x, lp["wqkv"], lp["bqkv"], 3 * D, D)
             att = torch.empty(R, D, **f32)
             gated = cfg.gru_rel_pos and relb is not None
-            lib.call("sed_attention_relpos", qkv.data_ptr(), relb.data_ptr() if relb is not None else None,
+            # (the `attn_valu` tuning key selects the vector-pipe kernel in both modes: it has no single-product form)
+            lib.call("sed_attention_relpos_bf16x1" if one and not _lib.get_tuning("attn_valu") else "sed_attention_relpos", qkv.data_ptr(), relb.data_ptr() if relb is not None else None,
                      a.grep_linear.weight.data_ptr() if gated else None, a.grep_linear.bias.data_ptr() if gated else None,
                      lp["grep_a"].data_ptr() if gated else None, att.data_ptr(), B, T, H, D // H, st)
             o = linear(att, a.out_proj.weight, a.out_proj.bias, D, D)
@@ -366,7 +409,7 @@ class BEATs(nn.Module):
             h2 = None
             if ffn_tiles:
                 linear_tiles(ximg2, lyr.fc1.weight, lyr.fc1.bias, Fd, D, act=1, out_image=himg)
-                if LINEAR_TILES_KSPLIT and (Fd // 16) % 2 == 0:
+                if LINEAR_TILES_KSPLIT and (Fd // (32 if one else 16)) % 2 == 0:
                     # N = 768: 279 tiles on 256 CUs would be two rounds; two K halves = 558 items = three half-rounds, the partial sums
                     # added by the LayerNorm that follows
                     hh = linear_tiles(himg, lyr.fc2.weight, lyr.fc2.bias, D, Fd, split2=True)
@@ -385,16 +428,22 @@ class BEATs(nn.Module):
 class BEATsModel(nn.Module):
     """BEATs.py:205-223: loads `{"cfg", "model"}` from `cfg_path`; forward(x (B, N) waveforms) -> global / frame embeddings."""
 
-    def __init__(self, cfg_path=None, checkpoint=None):
+    def __init__(self, cfg_path=None, checkpoint=None, precision=None):
         super().__init__()
+        precision = resolve_precision(precision)         # (before the checkpoint is read: a wrong mode fails at once)
         if checkpoint is None:
             checkpoint = torch.load(cfg_path, map_location="cpu", weights_only=False)
         cfg = BEATsConfig(checkpoint["cfg"])
         model = BEATs(cfg)
         model.load_state_dict(checkpoint["model"])
+        model.set_precision(precision)
         self.model = model
         self.ckpt = checkpoint
         self.eval()
+
+    def set_precision(self, mode):
+        self.model.set_precision(mode)
+        return self
 
     def forward(self, x):
         features = self.model.extract_features(x)[0]

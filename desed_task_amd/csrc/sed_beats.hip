@@ -168,7 +168,9 @@ SED_API int sed_layernorm(const float* x, const float* res, float alpha, const f
 // (sed_gemm_bf16.hip, sed_linear_tiles_bf16x3: block (row / 256, c / 16) = [hi | lo][256][16], octet o of row r at slot o ^ ((r >> 3) & 1)).
 // A lane owns 4 consecutive channels (float4 in, float4 out, one 8-byte piece per plane); D % 256 == 0.  The sums run in a different
 // order than layernorm_kernel's (4 channels per lane instead of every 64th), so y agrees with it to rounding, not bit for bit.
-template <int NV>
+// <NV, SedOneProduct> (sed_layernorm_tiles_bf16x1): the same y, and only the single-product image of sed_split_tiles_bf16x1 -- block (row / 256,
+// c / 32) = [k half][256][16], each value rounded once.
+template <int NV, class... ONE>
 __global__ __launch_bounds__(256) void layernorm_tiles_kernel(const float* __restrict__ x, const float* __restrict__ x2, const float* __restrict__ res, float alpha,
                                                               const float* __restrict__ gamma, const float* __restrict__ beta,
                                                               float* __restrict__ y, unsigned short* __restrict__ yt, int Mrows, float eps) {
@@ -215,12 +217,18 @@ __global__ __launch_bounds__(256) void layernorm_tiles_kernel(const float* __res
         const float4 o = make_float4((v[u].x - mean) * inv * g.x + b.x, (v[u].y - mean) * inv * g.y + b.y, (v[u].z - mean) * inv * g.z + b.z,
                                      (v[u].w - mean) * inv * g.w + b.w);
         *(float4*)(y + (size_t)row * D + c) = o;
+        if constexpr (sed_np<ONE...>() == 1) {
+            // K tile c >> 5, half (c >> 4) & 1: the 16-channel plane c >> 4 of the panel, 4096 values each
+            unsigned short* d = yt + ((size_t)panel * (D / 16) + (c >> 4)) * 4096 + r8 * 16 + ((((c >> 3) & 1) ^ ((r8 >> 3) & 1)) << 3) + (c & 7);
+            *(uint2*)d = make_uint2(bf16_round2(o.x, o.y), bf16_round2(o.z, o.w));
+        } else {
         unsigned h0, l0, h1, l1;
         bf16_split2(o.x, o.y, h0, l0);
         bf16_split2(o.z, o.w, h1, l1);
         unsigned short* d = yt + ((size_t)panel * (D / 16) + (c >> 4)) * 8192 + r8 * 16 + ((((c >> 3) & 1) ^ ((r8 >> 3) & 1)) << 3) + (c & 7);
         *(uint2*)d = make_uint2(h0, h1);
         *(uint2*)(d + 4096) = make_uint2(l0, l1);
+        }
     }
 }
 SED_API int sed_layernorm_tiles(const float* x, const float* x2, const float* res, float alpha, const float* gamma, const float* beta, float* y,
@@ -231,6 +239,18 @@ SED_API int sed_layernorm_tiles(const float* x, const float* x2, const float* re
     const dim3 grid((M + 3) / 4);
 #define LN_CASE(d) \
     if (D == d) { SED_LAUNCH((layernorm_tiles_kernel<d / 256>), grid, dim3(256), 0, s, x, x2, res, alpha, gamma, beta, y, yt, M, eps); return sed_check_launch(); }
+    LN_CASE(256) LN_CASE(512) LN_CASE(768) LN_CASE(1024)
+#undef LN_CASE
+    return SED_ERR_UNSUPPORTED;
+}
+SED_API int sed_layernorm_tiles_bf16x1(const float* x, const float* x2, const float* res, float alpha, const float* gamma, const float* beta, float* y,
+                                       unsigned short* yt, int M, int D, float eps, void* stream) {
+    if (!x || !gamma || !beta || !y || !yt || M < 0) return SED_ERR_ARG;
+    if (M == 0) return SED_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((M + 3) / 4);
+#define LN_CASE(d) \
+    if (D == d) { SED_LAUNCH((layernorm_tiles_kernel<d / 256, SedOneProduct>), grid, dim3(256), 0, s, x, x2, res, alpha, gamma, beta, y, yt, M, eps); return sed_check_launch(); }
     LN_CASE(256) LN_CASE(512) LN_CASE(768) LN_CASE(1024)
 #undef LN_CASE
     return SED_ERR_UNSUPPORTED;
@@ -311,26 +331,34 @@ __global__ __launch_bounds__(256) void posconv_kernel(const float* __restrict__ 
 // from the frozen weights, split into bf16 hi / lo planes ONCE on the host side (beats.py::_pack), streamed through LDS four
 // taps at a time by plain 16-byte copies.  Workgroup = 64 tokens x one group, wave = 16 tokens x the 48 output channels.
 // ---------------------------------------------------------------------------------------------
+// <SedOneProduct> (sed_posconv_bf16x1): x and the weights rounded once, one MFMA per product -- the hi planes alone (wsplit is the hi plane
+// only: 4.5 sixteen-byte pieces per thread and chunk, the fifth by the lower half of the workgroup), half the LDS.
 #define PCM_TT 64
 #define PCM_KC 4
+template <class... ONE>
 __global__ __launch_bounds__(256) void posconv_mfma_kernel(const float* __restrict__ x, const unsigned short* __restrict__ wsplit,
                                                            const float* __restrict__ bias, float* __restrict__ y, int T, int D, int K,
                                                            int G) {
     SED_DYN_SMEM(smem);
+    constexpr int NP = sed_np<ONE...>(), PLANES = NP == 1 ? 1 : 2;
     const int nrows = PCM_TT + K - 1, XPL = nrows * PC_CG, WPL = PCM_KC * PC_CG * PC_CG;
     unsigned short* xh = (unsigned short*)smem;           // [nrows][48] hi | lo
-    unsigned short* wh = xh + 2 * XPL;                    // [PCM_KC][48 co][48 ci] hi | lo
+    unsigned short* wh = xh + PLANES * XPL;               // [PCM_KC][48 co][48 ci] hi | lo
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, i16 = lane & 15, g = lane >> 4;
     const int t0 = blockIdx.x * PCM_TT, grp = blockIdx.y, b = blockIdx.z, half = K / 2;
     for (int i = tid; i < nrows * (PC_CG / 4); i += 256) {
         const int r = i / (PC_CG / 4), c4 = i - r * (PC_CG / 4), t = t0 - half + r;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (t >= 0 && t < T) v = *(const float4*)(x + ((size_t)b * T + t) * D + grp * PC_CG + 4 * c4);
+        if constexpr (NP == 1) {
+            *(uint2*)(xh + r * PC_CG + 4 * c4) = make_uint2(bf16_round2(v.x, v.y), bf16_round2(v.z, v.w));
+        } else {
         uint2 hv, lv;
         bf16_split2(v.x, v.y, hv.x, lv.x);
         bf16_split2(v.z, v.w, hv.y, lv.y);
         *(uint2*)(xh + r * PC_CG + 4 * c4) = hv;
         *(uint2*)(xh + XPL + r * PC_CG + 4 * c4) = lv;
+        }
     }
     f32x4 acc[3];
 #pragma unroll
@@ -347,8 +375,10 @@ __global__ __launch_bounds__(256) void posconv_mfma_kernel(const float* __restri
     const unsigned short* const ws##q = wsplit + (size_t)grp * K * PC_CG * PC_CG + wp##q * plane + 8 * (size_t)we##q;        \
     unsigned short* const wd##q = wh + wp##q * WPL + 8 * we##q;
     PCM_EACH(PCM_DECL)
-#define PCM_LOAD(q) w##q = *(const uint4*)(ws##q + koff);
-#define PCM_PARK(q) *(uint4*)wd##q = w##q;
+    // (one product: pieces 0 .. 1151 are the hi plane -- q = 0 .. 3 whole, q = 4 for tid < 128; no piece of a second plane is touched)
+#define PCM_LIVE(q) (NP != 1 || (q) < 4 || ((q) == 4 && tid < 128))
+#define PCM_LOAD(q) if (PCM_LIVE(q)) w##q = *(const uint4*)(ws##q + koff);
+#define PCM_PARK(q) if (PCM_LIVE(q)) *(uint4*)wd##q = w##q;
     {
         const size_t koff = 0;
         PCM_EACH(PCM_LOAD)
@@ -365,6 +395,12 @@ __global__ __launch_bounds__(256) void posconv_mfma_kernel(const float* __restri
         for (int ks = 0; ks < PCM_KC * PC_CG / 32; ++ks) {                       // 6 k-steps of 32 = 4 octets of (tap, 8 channels)
             const int o = 4 * ks + g, tapl = o / (PC_CG / 8), c8 = o - tapl * (PC_CG / 8);
             const unsigned short* ap = xh + (16 * w + i16 + k0 + tapl) * PC_CG + 8 * c8;
+            if constexpr (NP == 1) {
+                const s16x8 ah = *(const s16x8*)ap;
+#pragma unroll
+                for (int nb = 0; nb < 3; ++nb)
+                    acc[nb] = mfma16_bf16(ah, *(const s16x8*)(wh + (tapl * PC_CG + 16 * nb + i16) * PC_CG + 8 * c8), acc[nb]);
+            } else {
             const s16x8 ah = *(const s16x8*)ap, al = *(const s16x8*)(ap + XPL);
 #pragma unroll
             for (int nb = 0; nb < 3; ++nb) {
@@ -373,6 +409,7 @@ __global__ __launch_bounds__(256) void posconv_mfma_kernel(const float* __restri
                 acc[nb] = mfma16_bf16(al, bh, acc[nb]);
                 acc[nb] = mfma16_bf16(ah, bl, acc[nb]);
                 acc[nb] = mfma16_bf16(ah, bh, acc[nb]);
+            }
             }
         }
     }
@@ -397,9 +434,21 @@ SED_API int sed_posconv_bf16x3(const float* x, const unsigned short* wsplit, con
     if (B <= 0 || T <= 0) return SED_OK;
     const int smem = (2 * (PCM_TT + K - 1) * PC_CG + 2 * PCM_KC * PC_CG * PC_CG) * 2;
     if (smem > 150 * 1024) return SED_ERR_UNSUPPORTED;
-    SED_MAX_SMEM(posconv_mfma_kernel, smem);
-    SED_LAUNCH(posconv_mfma_kernel, dim3((T + PCM_TT - 1) / PCM_TT, groups, B), dim3(256), smem, (hipStream_t)stream, x, wsplit, bias, y,
+    SED_MAX_SMEM(posconv_mfma_kernel<>, smem);
+    SED_LAUNCH(posconv_mfma_kernel<>, dim3((T + PCM_TT - 1) / PCM_TT, groups, B), dim3(256), smem, (hipStream_t)stream, x, wsplit, bias, y,
                T, D, K, groups);
+    return sed_check_launch();
+}
+// whi: (groups, K, 48 co, 48 ci) bf16 bit patterns of the weight-normalised filter, rounded once (the hi plane of wsplit alone)
+SED_API int sed_posconv_bf16x1(const float* x, const unsigned short* whi, const float* bias, float* y, int B, int T, int D, int K,
+                               int groups, void* stream) {
+    if (groups < 1 || D % groups != 0 || D / groups != PC_CG || K < 2 || (K & 1) || K % PCM_KC != 0 || D % 4 != 0) return SED_ERR_UNSUPPORTED;
+    if (B <= 0 || T <= 0) return SED_OK;
+    const int smem = ((PCM_TT + K - 1) * PC_CG + PCM_KC * PC_CG * PC_CG) * 2;
+    if (smem > 150 * 1024) return SED_ERR_UNSUPPORTED;
+    SED_MAX_SMEM(posconv_mfma_kernel<SedOneProduct>, smem);
+    SED_LAUNCH(posconv_mfma_kernel<SedOneProduct>, dim3((T + PCM_TT - 1) / PCM_TT, groups, B), dim3(256), smem, (hipStream_t)stream, x, whi, bias,
+               y, T, D, K, groups);
     return sed_check_launch();
 }
 
@@ -554,17 +603,22 @@ __device__ __forceinline__ float atm_exp2(float x) {
     return __builtin_amdgcn_exp2f(x);
 #endif
 }
-template <bool BIAS>
+// <BIAS, SedOneProduct> (sed_attention_relpos_bf16x1): Q (scale log2 e), K, V^T and P as SINGLE bf16 fragments, one MFMA per product -- no lo
+// planes are formed, staged or reserved; the probabilities are rounded once where they become the B operand, the running sum takes the
+// unrounded fp32 values; gate, bias staging and softmax arithmetic are the code below unchanged.
+template <bool BIAS, class... ONE>
 __global__ __launch_bounds__(256, 2) void attention_mfma_kernel(const float* __restrict__ qkv, const float* __restrict__ relb,
                                                              const float* __restrict__ grep_w, const float* __restrict__ grep_b,
                                                              const float* __restrict__ grep_a, float* __restrict__ out, int T, int H,
                                                              int n_pairs, float scaling) {
     SED_DYN_SMEM(smem);
+    constexpr int NP = sed_np<ONE...>(), PLANES = NP == 1 ? 1 : 2;
     unsigned short* kh = (unsigned short*)smem;           // K   [64 keys][ATM_P] hi | lo
     unsigned short* kl = kh + 64 * ATM_P;
-    unsigned short* vh = kl + 64 * ATM_P;                 // V^T [64 dims][ATM_P] hi | lo, keys in MFMA-slot order
+    unsigned short* vh = kh + PLANES * 64 * ATM_P;        // V^T [64 dims][ATM_P] hi | lo, keys in MFMA-slot order
     unsigned short* vl = vh + 64 * ATM_P;
-    float* rb = (float*)(vl + 64 * ATM_P);                // [2 T - 1 (+ 64 zeros)] bias row of this head, times log2 e
+    float* rb = (float*)(vh + PLANES * 64 * ATM_P);       // [2 T - 1 (+ 64 zeros)] bias row of this head, times log2 e
+    (void)kl; (void)vl;
     const float LOG2E = 1.44269504088896341f;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, i16 = lane & 15, g = lane >> 4;
     // XCD-aware walk: workgroup n runs on XCD n & 7; the query tiles of one (b, h) are consecutive workgroups OF ONE XCD, so that head's
@@ -618,7 +672,10 @@ __global__ __launch_bounds__(256, 2) void attention_mfma_kernel(const float* __r
         for (int ks = 0; ks < 2; ++ks) {
             unsigned hv[4], lv[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) bf16_split2(qv[8 * ks + 2 * e] * qs, qv[8 * ks + 2 * e + 1] * qs, hv[e], lv[e]);
+            for (int e = 0; e < 4; ++e) {
+                if constexpr (NP == 1) { hv[e] = bf16_round2(qv[8 * ks + 2 * e] * qs, qv[8 * ks + 2 * e + 1] * qs); lv[e] = 0u; }
+                else bf16_split2(qv[8 * ks + 2 * e] * qs, qv[8 * ks + 2 * e + 1] * qs, hv[e], lv[e]);
+            }
             uint4 hq, lq;
             hq.x = hv[0]; hq.y = hv[1]; hq.z = hv[2]; hq.w = hv[3];
             lq.x = lv[0]; lq.y = lv[1]; lq.z = lv[2]; lq.w = lv[3];
@@ -660,18 +717,26 @@ __global__ __launch_bounds__(256, 2) void attention_mfma_kernel(const float* __r
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {                              // K rows: dims 4 kq .. + 3 of key dq + 16 j
+                if constexpr (NP == 1) {
+                    *(uint2*)(kh + (dq + 16 * j) * ATM_P + 4 * kq) = make_uint2(bf16_round2(kr[j].x, kr[j].y), bf16_round2(kr[j].z, kr[j].w));
+                } else {
                 uint2 hv, lv;
                 bf16_split2(kr[j].x, kr[j].y, hv.x, lv.x);
                 bf16_split2(kr[j].z, kr[j].w, hv.y, lv.y);
                 *(uint2*)(kh + (dq + 16 * j) * ATM_P + 4 * kq) = hv;
                 *(uint2*)(kl + (dq + 16 * j) * ATM_P + 4 * kq) = lv;
+                }
             }
             auto vt = [&](float a, float c, float e, float f, int d) {  // V^T rows: 4 keys of dim d
+                if constexpr (NP == 1) {
+                    *(uint2*)(vh + d * ATM_P + vpos) = make_uint2(bf16_round2(a, c), bf16_round2(e, f));
+                } else {
                 uint2 hv, lv;
                 bf16_split2(a, c, hv.x, lv.x);
                 bf16_split2(e, f, hv.y, lv.y);
                 *(uint2*)(vh + d * ATM_P + vpos) = hv;
                 *(uint2*)(vl + d * ATM_P + vpos) = lv;
+                }
             };
             vt(vr[0].x, vr[1].x, vr[2].x, vr[3].x, 4 * dq);
             vt(vr[0].y, vr[1].y, vr[2].y, vr[3].y, 4 * dq + 1);
@@ -688,6 +753,11 @@ __global__ __launch_bounds__(256, 2) void attention_mfma_kernel(const float* __r
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 const unsigned short* ap = kh + (16 * kb + i16) * ATM_P + 32 * ks + 8 * g;
+                if constexpr (NP == 1) {
+                    const s16x8 ah = *(const s16x8*)ap;
+                    a0 = mfma16_bf16(ah, qh[0][ks], a0);
+                    a1 = mfma16_bf16(ah, qh[1][ks], a1);
+                } else {
                 const s16x8 ah = *(const s16x8*)ap, al = *(const s16x8*)(ap + 64 * ATM_P);
                 a0 = mfma16_bf16(al, qh[0][ks], a0);
                 a1 = mfma16_bf16(al, qh[1][ks], a1);
@@ -695,6 +765,7 @@ __global__ __launch_bounds__(256, 2) void attention_mfma_kernel(const float* __r
                 a1 = mfma16_bf16(ah, ql[1][ks], a1);
                 a0 = mfma16_bf16(ah, qh[0][ks], a0);
                 a1 = mfma16_bf16(ah, qh[1][ks], a1);
+                }
             }
             sc[0][kb] = a0;
             sc[1][kb] = a1;
@@ -752,10 +823,18 @@ __global__ __launch_bounds__(256, 2) void attention_mfma_kernel(const float* __r
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
                     uint4 hq, lq;
+                    if constexpr (NP == 1) {                          // rounded once, here, where P becomes an MFMA operand
+                        hq.x = bf16_round2(sc[j][2 * ks][0], sc[j][2 * ks][1]);
+                        hq.y = bf16_round2(sc[j][2 * ks][2], sc[j][2 * ks][3]);
+                        hq.z = bf16_round2(sc[j][2 * ks + 1][0], sc[j][2 * ks + 1][1]);
+                        hq.w = bf16_round2(sc[j][2 * ks + 1][2], sc[j][2 * ks + 1][3]);
+                        lq = make_uint4(0u, 0u, 0u, 0u);
+                    } else {
                     bf16_split2(sc[j][2 * ks][0], sc[j][2 * ks][1], hq.x, lq.x);
                     bf16_split2(sc[j][2 * ks][2], sc[j][2 * ks][3], hq.y, lq.y);
                     bf16_split2(sc[j][2 * ks + 1][0], sc[j][2 * ks + 1][1], hq.z, lq.z);
                     bf16_split2(sc[j][2 * ks + 1][2], sc[j][2 * ks + 1][3], hq.w, lq.w);
+                    }
                     ph[j][ks] = __builtin_bit_cast(s16x8, hq);
                     pl[j][ks] = __builtin_bit_cast(s16x8, lq);
                 }
@@ -768,6 +847,11 @@ __global__ __launch_bounds__(256, 2) void attention_mfma_kernel(const float* __r
 #pragma unroll
             for (int db = 0; db < 4; ++db) {
                 const unsigned short* ap = vh + (16 * db + i16) * ATM_P + 32 * ks + 8 * g;
+                if constexpr (NP == 1) {
+                    const s16x8 ah = *(const s16x8*)ap;
+                    o[0][db] = mfma16_bf16(ah, ph[0][ks], o[0][db]);
+                    o[1][db] = mfma16_bf16(ah, ph[1][ks], o[1][db]);
+                } else {
                 const s16x8 ah = *(const s16x8*)ap, al = *(const s16x8*)(ap + 64 * ATM_P);
                 o[0][db] = mfma16_bf16(al, ph[0][ks], o[0][db]);
                 o[1][db] = mfma16_bf16(al, ph[1][ks], o[1][db]);
@@ -775,6 +859,7 @@ __global__ __launch_bounds__(256, 2) void attention_mfma_kernel(const float* __r
                 o[1][db] = mfma16_bf16(ah, pl[1][ks], o[1][db]);
                 o[0][db] = mfma16_bf16(ah, ph[0][ks], o[0][db]);
                 o[1][db] = mfma16_bf16(ah, ph[1][ks], o[1][db]);
+                }
             }
     }
 #pragma unroll
@@ -809,5 +894,25 @@ SED_API int sed_attention_relpos(const float* qkv, const float* relb, const floa
     SED_MAX_SMEM(attention_kernel, smem);
     SED_LAUNCH(attention_kernel, dim3((T + AT_TQ - 1) / AT_TQ, H, B), dim3(256), smem, (hipStream_t)stream, qkv, relb, grep_w, grep_b,
                grep_a, out, T, H, 1.0f / sqrtf((float)head_dim));
+    return sed_check_launch();
+}
+
+// The single-product twin of the matrix-core kernel (the extractor's "bf16" mode): same arguments, same grid; half the K / V planes in LDS.
+// The vector-pipe kernel has no single-product form: with the `attn_valu` tuning key set the caller selects sed_attention_relpos.
+SED_API int sed_attention_relpos_bf16x1(const float* qkv, const float* relb, const float* grep_w, const float* grep_b,
+                                        const float* grep_a, float* out, int B, int T, int H, int head_dim, void* stream) {
+    if (head_dim != AT_HD || T > 4096) return SED_ERR_UNSUPPORTED;
+    if (B <= 0 || T <= 0) return SED_OK;
+    const int smem_m = 2 * 64 * ATM_P * 2 + (64 + 2 * T) * 4;
+    const int nwg = ((T + ATM_QG - 1) / ATM_QG) * ((H * B + 7) / 8) * 8;
+    if (relb) {
+        SED_MAX_SMEM((attention_mfma_kernel<true, SedOneProduct>), smem_m);
+        SED_LAUNCH((attention_mfma_kernel<true, SedOneProduct>), dim3(nwg), dim3(256), smem_m, (hipStream_t)stream, qkv, relb,
+                   grep_w, grep_b, grep_a, out, T, H, H * B, 1.0f / sqrtf((float)head_dim));
+    } else {
+        SED_MAX_SMEM((attention_mfma_kernel<false, SedOneProduct>), smem_m);
+        SED_LAUNCH((attention_mfma_kernel<false, SedOneProduct>), dim3(nwg), dim3(256), smem_m, (hipStream_t)stream, qkv, relb,
+                   grep_w, grep_b, grep_a, out, T, H, H * B, 1.0f / sqrtf((float)head_dim));
+    }
     return sed_check_launch();
 }

@@ -564,6 +564,25 @@ __global__ __launch_bounds__(256) void split_tiles_kernel(const float* __restric
     }
 }
 
+// The single-product image (the "bf16" mode of the extractor, sed_split_tiles_bf16x1): the SAME block geometry, the two planes of a block
+// now being the two 16-deep halves of a 32-deep K tile -- block (row panel, k / 32) = [k half][256 rows][16], each value rounded once.
+__global__ __launch_bounds__(256) void split_tiles1_kernel(const float* __restrict__ X, unsigned short* __restrict__ Xt, int R, int K, int nkt) {
+    const int blk = blockIdx.x, panel = blk / nkt, kt = blk - panel * nkt, tid = threadIdx.x;
+    unsigned short* dst = Xt + (size_t)blk * T_BLOCK;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int half = u >> 1, row = (tid >> 1) + 128 * (u & 1), slot = tid & 1, oct = slot ^ ((row >> 3) & 1), r = panel * 256 + row;
+        float4 p = make_float4(0.f, 0.f, 0.f, 0.f), q = p;
+        if (r < R) {
+            const float* src = X + (size_t)r * K + kt * 2 * T_BK + half * T_BK + 8 * oct;
+            p = *(const float4*)src;
+            q = *(const float4*)(src + 4);
+        }
+        const uint2 a = round4(p), b = round4(q);
+        *(uint4*)(dst + half * T_PLANE + row * T_BK + 8 * slot) = make_uint4(a.x, a.y, b.x, b.y);
+    }
+}
+
 // T_STAMP (diagnostics build only: ONLY=sed_gemm_bf16.hip python tools/build_variant.py tstamp -DT_STAMP; tools/linear_stamps.py): s_memtime
 // at the seams of a phase -- start, DMA issued + fragments landed, first barrier passed, MFMAs issued, second barrier passed (second phase:
 // + after the vmcnt wait) -- for wave 0 (group 0) and wave 4 (group 1) of workgroup 64, K tiles 8 .. 23, kept in the 32 KB of LDS the
@@ -587,11 +606,16 @@ SED_API int sed_linear_debug_set_stamps(unsigned long long* buf) {
 // = A fragment: a lane then holds one row m and 4 consecutive columns n per register quad): C leaves as 16-byte stores, or (OUT = 1) as
 // 8-byte hi / lo pieces straight into the K-tiled image the NEXT Linear reads (fc1's GELU output -> fc2), rows of the padded last panel
 // included.
-template <int ACT, int OUT>
+// <..., SedOneProduct> (the *_bf16x1 entries): the images are the single-product ones, a K step is 32 deep -- the stage's "hi" blocks hold k 0 .. 15 of
+// the step, its "lo" blocks k 16 .. 31 -- and a phase issues, per accumulator, the product of the first halves and then of the second: 8 MFMAs
+// over twice the depth.  DMA pieces, stages, waits and barriers are the same instructions; per output element the chain is still "ascending
+// k, one 32x32x16 MFMA per 16 k", which is what the three-product form computes on operands whose lo planes are zero.
+template <int ACT, int OUT, class... ONE>
 __global__ __launch_bounds__(512, 1) void linear_dma_kernel(const unsigned short* __restrict__ At, const unsigned short* __restrict__ Wt,
                                                            const float* __restrict__ bias, void* __restrict__ Cout, int M, int N, int K,
                                                            int tiles_m, int tiles_n, int nvb, int skew, int ksplit) {
     SED_DYN_SMEM(smem);                               // [4 stages][A hi | A lo | W hi | W lo][256][16] bf16
+    constexpr int NP = sed_np<ONE...>(), KSTEP = NP == 1 ? 2 * T_BK : T_BK;
     unsigned short* lds = (unsigned short*)smem;
     const int tid = threadIdx.x, lane = tid & 63, w = sed_wave_uniform(tid >> 6), lo = lane & 31, hi = lane >> 5;
     const int wr = w >> 2, wc = w & 3;                // wave: rows 128 wr .. + 127, columns 64 wc .. + 63 of the tile; group = wr
@@ -599,7 +623,7 @@ __global__ __launch_bounds__(512, 1) void linear_dma_kernel(const unsigned short
     // virtual block -> tile: XCD x = vb & 7 owns the row panels tm = x (mod 8) and sweeps their N tiles back to back.  With ksplit = 2 a
     // work item is (tile, K half): items [0, nvb) are the first halves, [nvb, 2 nvb) the second (nvb is a multiple of 8: same XCD), each
     // writing its own partial C -- 279 tiles on 256 CUs are two rounds, 558 half-items three half-rounds (the N = 768 layers).
-    const int nk = K / T_BK / ksplit, nwi = nvb * ksplit;          // K steps per work item
+    const int nk = K / KSTEP / ksplit, nwi = nvb * ksplit;         // K steps per work item
     auto valid = [&](int wi) { const int vb = wi >= nvb ? wi - nvb : wi; return (vb & 7) + 8 * ((vb >> 3) / tiles_n) < tiles_m; };
     auto next_vb = [&](int wi) { do wi += gstride; while (wi < nwi && !valid(wi)); return wi; };
     int cvb = (int)blockIdx.x;                        // compute cursor
@@ -664,13 +688,19 @@ __global__ __launch_bounds__(512, 1) void linear_dma_kernel(const unsigned short
 #ifndef T_DIAG
 #define T_DIAG 0            // timing-only builds: 1 no MFMAs, 2 no fragment reads, 4 no DMA (wrong results)
 #endif
-#define T_MFMA(h) do { sed_mfma_prio(1); if (!(T_DIAG & 1)) {                                                                    \
+#define T_MFMA(h) do { sed_mfma_prio(1); if (!(T_DIAG & 1)) { if constexpr (NP == 1) {                                            \
+        /* single product: k 0 .. 15 (the "hi" blocks), then k 16 .. 31 (the "lo" blocks) */                                      \
+        acc[2 * (h)][0] = mfma32_bf16(bh0, ah0, acc[2 * (h)][0]); acc[2 * (h)][1] = mfma32_bf16(bh1, ah0, acc[2 * (h)][1]);     \
+        acc[2 * (h) + 1][0] = mfma32_bf16(bh0, ah1, acc[2 * (h) + 1][0]); acc[2 * (h) + 1][1] = mfma32_bf16(bh1, ah1, acc[2 * (h) + 1][1]); \
+        acc[2 * (h)][0] = mfma32_bf16(bl0, al0, acc[2 * (h)][0]); acc[2 * (h)][1] = mfma32_bf16(bl1, al0, acc[2 * (h)][1]);     \
+        acc[2 * (h) + 1][0] = mfma32_bf16(bl0, al1, acc[2 * (h) + 1][0]); acc[2 * (h) + 1][1] = mfma32_bf16(bl1, al1, acc[2 * (h) + 1][1]); \
+        } else {                                                                                                                  \
         acc[2 * (h)][0] = mfma32_bf16(bh0, al0, acc[2 * (h)][0]); acc[2 * (h)][1] = mfma32_bf16(bh1, al0, acc[2 * (h)][1]);     \
         acc[2 * (h) + 1][0] = mfma32_bf16(bh0, al1, acc[2 * (h) + 1][0]); acc[2 * (h) + 1][1] = mfma32_bf16(bh1, al1, acc[2 * (h) + 1][1]); \
         acc[2 * (h)][0] = mfma32_bf16(bl0, ah0, acc[2 * (h)][0]); acc[2 * (h)][1] = mfma32_bf16(bl1, ah0, acc[2 * (h)][1]);     \
         acc[2 * (h) + 1][0] = mfma32_bf16(bl0, ah1, acc[2 * (h) + 1][0]); acc[2 * (h) + 1][1] = mfma32_bf16(bl1, ah1, acc[2 * (h) + 1][1]); \
         acc[2 * (h)][0] = mfma32_bf16(bh0, ah0, acc[2 * (h)][0]); acc[2 * (h)][1] = mfma32_bf16(bh1, ah0, acc[2 * (h)][1]);     \
-        acc[2 * (h) + 1][0] = mfma32_bf16(bh0, ah1, acc[2 * (h) + 1][0]); acc[2 * (h) + 1][1] = mfma32_bf16(bh1, ah1, acc[2 * (h) + 1][1]); } \
+        acc[2 * (h) + 1][0] = mfma32_bf16(bh0, ah1, acc[2 * (h) + 1][0]); acc[2 * (h) + 1][1] = mfma32_bf16(bh1, ah1, acc[2 * (h) + 1][1]); } } \
         sed_mfma_prio(0); } while (0)
 #ifdef T_STAMP
     unsigned long long* s_ts = (unsigned long long*)(lds + 4 * T_STAGE);
@@ -737,6 +767,9 @@ __global__ __launch_bounds__(512, 1) void linear_dma_kernel(const unsigned short
                     }
                     if (OUT == 0) {
                         if ((T_DIAG & 8) ? (v.x == 1.2345e-30f) : (m0 + mrow < M)) *(float4*)(Cpart + (size_t)(m0 + mrow) * N + gn) = v;
+                    } else if constexpr (NP == 1) {
+                        // column gn of the next Linear's single-product image: K tile gn >> 5, half (gn >> 4) & 1 = 16-column plane gn >> 4
+                        *(uint2*)((unsigned short*)Cout + ((size_t)tm * (N / T_BK) + (gn >> 4)) * T_PLANE + t_off(mrow, q & 1) + 4 * ehi) = round4(v);
                     } else {
                         uint2 h_, l_;
                         split4(v, h_, l_);
@@ -964,12 +997,13 @@ __global__ __launch_bounds__(640, 1) void linear_ldr_kernel(const unsigned short
 }  // namespace
 
 static int linear_tiles_launch(const unsigned short* At, const unsigned short* Wt, const float* bias, void* Cout, int M, int N, int K, int act,
-                               int out_tiles, void* stream, int ksplit = 1) {
+                               int out_tiles, void* stream, int ksplit = 1, bool single = false) {
     if (!At || !Wt || !Cout || M < 0 || N < 0 || K < 0) return SED_ERR_ARG;
     if (act < 0 || act > 1) return SED_ERR_ARG;
     if (M <= 0 || N <= 0) return SED_OK;
-    if (ksplit == 2 && (act != 0 || out_tiles || (K / T_BK) % 2 != 0)) return SED_ERR_UNSUPPORTED;
-    if (N % P_BN != 0 || K % T_BK != 0 || K <= 0 || ((uintptr_t)At & 15) || ((uintptr_t)Wt & 15) || ((uintptr_t)Cout & 15) || ((uintptr_t)bias & 15))
+    const int kstep = single ? 2 * T_BK : T_BK;       // (the single-product images are cut into 32-deep K tiles)
+    if (ksplit == 2 && (act != 0 || out_tiles || (K / kstep) % 2 != 0)) return SED_ERR_UNSUPPORTED;
+    if (N % P_BN != 0 || K % kstep != 0 || K <= 0 || ((uintptr_t)At & 15) || ((uintptr_t)Wt & 15) || ((uintptr_t)Cout & 15) || ((uintptr_t)bias & 15))
         return SED_ERR_UNSUPPORTED;
     const int tm = (M + P_BM - 1) / P_BM, tn = N / P_BN;
     const long long nvb_ll = 8LL * ((tm + 7) / 8) * tn;
@@ -991,6 +1025,9 @@ static int linear_tiles_launch(const unsigned short* At, const unsigned short* W
     const long long ntiles = (long long)tm * tn * ksplit;
     int skew = (ntiles > grid && ntiles % grid != 0) ? (int)((ntiles + grid - 1) / grid) : 0;
     if (sed_tuning[SED_TUNE_LINEAR_TILES] == 3) skew = 0;
+    // The single-product entries: always the eight-wave form (the loader-wave form is three-product only; a grid request n > 8 still holds),
+    // and no start skew -- its nk * 2800 ticks per K step were fitted to the three-product step and have not been re-fitted.
+    if (single) { ldr = false; skew = 0; }
 #ifdef T_STAMP
     constexpr int SMEM_T = 4 * T_STAGE * 2 + 8192;
 #else
@@ -1000,8 +1037,15 @@ static int linear_tiles_launch(const unsigned short* At, const unsigned short* W
         SED_LAUNCH((linear_ldr_kernel<A_, O_>), dim3((unsigned)grid), dim3(640), SMEM_T, (hipStream_t)stream, At, Wt, bias, Cout, M, N, K, tm, tn, nvb); } \
         else { SED_MAX_SMEM((linear_dma_kernel<A_, O_>), SMEM_T);                                                               \
         SED_LAUNCH((linear_dma_kernel<A_, O_>), dim3((unsigned)grid), dim3(512), SMEM_T, (hipStream_t)stream, At, Wt, bias, Cout, M, N, K, tm, tn, nvb, skew, ksplit); } } while (0)
-    if (out_tiles) { if (act) T_LAUNCH(1, 1); else T_LAUNCH(0, 1); }
+#define T_LAUNCH1(A_, O_) do { SED_MAX_SMEM((linear_dma_kernel<A_, O_, SedOneProduct>), SMEM_T);                                \
+        SED_LAUNCH((linear_dma_kernel<A_, O_, SedOneProduct>), dim3((unsigned)grid), dim3(512), SMEM_T, (hipStream_t)stream, At, Wt, bias, Cout, M, N, K, tm, tn, nvb, skew, ksplit); } while (0)
+    if (single) {
+        if (out_tiles) { if (act) T_LAUNCH1(1, 1); else T_LAUNCH1(0, 1); }
+        else { if (act) T_LAUNCH1(1, 0); else T_LAUNCH1(0, 0); }
+    }
+    else if (out_tiles) { if (act) T_LAUNCH(1, 1); else T_LAUNCH(0, 1); }
     else { if (act) T_LAUNCH(1, 0); else T_LAUNCH(0, 0); }
+#undef T_LAUNCH1
 #undef T_LAUNCH
     return sed_check_launch();
 }
@@ -1019,6 +1063,32 @@ SED_API int sed_linear_tiles_split2_bf16x3(const unsigned short* At, const unsig
 SED_API int sed_linear_tiles_out_bf16x3(const unsigned short* At, const unsigned short* Wt, const float* bias, unsigned short* Ct, int M, int N,
                                         int K, int act, void* stream) {
     return linear_tiles_launch(At, Wt, bias, Ct, M, N, K, act, 1, stream);
+}
+
+// ---- the single-product ("bf16") twins: the same kernel at one MFMA per product on the single-product image (include/sed_hip.h) ----
+SED_API int sed_split_tiles_bf16x1(const float* X, unsigned short* Xt, int R, int K, void* stream) {
+    if (!X || !Xt || R < 0 || K < 0) return SED_ERR_ARG;
+    if (R == 0 || K == 0) return SED_OK;
+    if (K % (2 * T_BK) != 0 || ((uintptr_t)X & 15) || ((uintptr_t)Xt & 15)) return SED_ERR_UNSUPPORTED;
+    const long long blocks = (long long)((R + 255) / 256) * (K / (2 * T_BK));
+    if (blocks > 0x7fffffffLL) return SED_ERR_UNSUPPORTED;
+    SED_LAUNCH(split_tiles1_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, X, Xt, R, K, K / (2 * T_BK));
+    return sed_check_launch();
+}
+
+SED_API int sed_linear_tiles_bf16x1(const unsigned short* At, const unsigned short* Wt, const float* bias, float* Cm, int M, int N, int K,
+                                    int act, void* stream) {
+    return linear_tiles_launch(At, Wt, bias, Cm, M, N, K, act, 0, stream, 1, true);
+}
+
+SED_API int sed_linear_tiles_split2_bf16x1(const unsigned short* At, const unsigned short* Wt, const float* bias, float* C2, int M, int N, int K,
+                                           void* stream) {
+    return linear_tiles_launch(At, Wt, bias, C2, M, N, K, 0, 0, stream, 2, true);
+}
+
+SED_API int sed_linear_tiles_out_bf16x1(const unsigned short* At, const unsigned short* Wt, const float* bias, unsigned short* Ct, int M, int N,
+                                        int K, int act, void* stream) {
+    return linear_tiles_launch(At, Wt, bias, Ct, M, N, K, act, 1, stream, 1, true);
 }
 
 namespace {
@@ -1064,4 +1134,12 @@ SED_API int sed_linear_bf16x3(const float* A, const float* W, const float* bias,
     if (act < 0 || act > 1) return SED_ERR_ARG;
     return gemmb_dispatch(A, W, bias, Cm, nullptr, nullptr, nullptr, nullptr, 1, M, N, K, K, K, N, 0, 1, 1, 0, (hipStream_t)stream,
                           nullptr, 0, act, nullptr, true);
+}
+
+// The single-product twin: both operands rounded once, one MFMA per product (gemm_bf16x3_kernel<.., SedOneProduct>), same tiles and walk.
+SED_API int sed_linear_bf16x1(const float* A, const float* W, const float* bias, float* Cm, int M, int N, int K, int act,
+                              void* stream) {
+    if (act < 0 || act > 1) return SED_ERR_ARG;
+    return gemmb_dispatch(A, W, bias, Cm, nullptr, nullptr, nullptr, nullptr, 1, M, N, K, K, K, N, 0, 1, 1, 0, (hipStream_t)stream,
+                          nullptr, 0, act, nullptr, true, true);
 }

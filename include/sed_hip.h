@@ -484,6 +484,32 @@ int sed_linear_tiles_split2_bf16x3(const unsigned short* At, const unsigned shor
 int sed_linear_tiles_out_bf16x3(const unsigned short* At, const unsigned short* Wt, const float* bias, unsigned short* Ct, int M, int N,
                                 int K, int act, void* stream);
 
+/* ---- the extractor's single-product "bf16" mode (BEATs.set_precision("bf16"); no reference counterpart: the reference runs fp32) ----
+ * Every *_bf16x1 entry below is the twin of the entry of the same name: same arguments, same argument checks, both operands of every
+ * contraction rounded ONCE to bf16 (round to nearest even -- the rounding that forms the hi planes), ONE MFMA per product, fp32
+ * accumulation in the same k order; bias, GELU, softmax, LayerNorm and residuals stay fp32.  On operands that are bf16 values already
+ * the Linear and position-convolution twins return the bits of the three-product entries.
+ *
+ * The single-product tile image (sed_split_tiles_bf16x1, sed_layernorm_tiles_bf16x1, sed_linear_tiles_out_bf16x1 write it; the
+ * sed_linear_tiles*_bf16x1 entries read it): X (R, K), K % 32 == 0, as ceil(R / 256) * (K / 32) blocks of 16 KB in (row panel, K tile)
+ * order -- the three-product block geometry, its two planes now being the two 16-deep halves of a 32-deep K tile:
+ *   block (r / 256, k / 32) = [k half (k / 16) & 1][256 rows][16] bf16 bit patterns of bf16(x);
+ *   the 8-k octet o = (k / 8) & 1 of row r of a half is stored at slot o ^ ((r >> 3) & 1);  rows >= R are zero.
+ * The image holds ceil(R / 256) * 256 * K 16-bit words: half of the three-product image. */
+int sed_linear_bf16x1(const float* A, const float* W, const float* bias, float* Cm, int M, int N, int K, int act, void* stream);
+int sed_split_tiles_bf16x1(const float* X, unsigned short* Xt, int R, int K, void* stream);
+/* N % 256 == 0, K % 32 == 0, 16-byte aligned.  Always the eight-wave kernel, launched without the start skew; the `linear_tiles` tuning
+ * key's grid request (n > 8: n & ~7 workgroups) holds. */
+int sed_linear_tiles_bf16x1(const unsigned short* At, const unsigned short* Wt, const float* bias, float* C, int M, int N, int K,
+                            int act, void* stream);
+/* (K / 32) even; no activation. */
+int sed_linear_tiles_split2_bf16x1(const unsigned short* At, const unsigned short* Wt, const float* bias, float* C2, int M, int N, int K,
+                                   void* stream);
+/* Ct: the single-product image of act(A . W^T + bias), ceil(M / 256) * 256 * N words, each value rounded once (backbone.py:279-283:
+ * fc1's GELU output as fc2's activation); every row of the padded last panel is written. */
+int sed_linear_tiles_out_bf16x1(const unsigned short* At, const unsigned short* Wt, const float* bias, unsigned short* Ct, int M, int N,
+                                int K, int act, void* stream);
+
 /* torchaudio.compliance.kaldi.fbank(waveform * 2^15, num_mel_bins, 16 kHz, 25 ms frames, 10 ms shift) with that function's
  * defaults (povey window, pre-emphasis 0.97, DC removal, snip_edges, 512-point FFT, power spectrum, log) followed by
  * (x - norm_mean) * norm_inv -- BEATs.preprocess, BEATs.py:109-133.  audio (B,N) -> out (B, 1 + (N - 400) / 160, n_mels).
@@ -508,6 +534,11 @@ int sed_layernorm(const float* x, const float* res, float alpha, const float* ga
 int sed_layernorm_tiles(const float* x, const float* x2, const float* res, float alpha, const float* gamma, const float* beta, float* y,
                         unsigned short* yt, int M, int D, float eps, void* stream);
 
+/* The single-product twin: the same fp32 y as sed_layernorm_tiles, bit for bit, and ONLY the single-product image described at
+ * sed_split_tiles_bf16x1 (yt: ceil(M / 256) * 256 * D words of bf16(y); rows >= M are left as they are). */
+int sed_layernorm_tiles_bf16x1(const float* x, const float* x2, const float* res, float alpha, const float* gamma, const float* beta,
+                               float* y, unsigned short* yt, int M, int D, float eps, void* stream);
+
 /* y = x + GELU(bias + grouped Conv1d(x)): the convolutional position embedding (backbone.py:30-43,118-120; even kernel, padding
  * K/2, last output dropped).  x, y (B,T,D); wt (groups, K, D/groups co, D/groups ci) = the weight-normalised filter transposed
  * on the host once. */
@@ -517,12 +548,22 @@ int sed_posconv(const float* x, const float* wt, const float* bias, float* y, in
 int sed_posconv_bf16x3(const float* x, const unsigned short* wsplit, const float* bias, float* y, int B, int T, int D, int K,
                        int groups, void* stream);
 
+/* The single-product twin: x and the filter rounded once.  whi: (groups, K, 48 co, 48 ci) = the hi plane of wsplit alone. */
+int sed_posconv_bf16x1(const float* x, const unsigned short* whi, const float* bias, float* y, int B, int T, int D, int K,
+                       int groups, void* stream);
+
 /* Multi-head self-attention of MultiheadAttention.forward (backbone.py:446-700, eval mode, no padding mask) on the output of ONE
  * fused q|k|v projection: qkv (B*T, 3*H*64) -> out (B*T, H*64).  relb (H, 2T-1) = relative position bias per offset s - t (the
  * bucket embedding of :390-444 gathered on the host), or null; grep_w (8,64), grep_b (8), grep_a (H) = the gate of :662-682, or
  * null for an ungated bias.  No T x T tensor is written to HBM. */
 int sed_attention_relpos(const float* qkv, const float* relb, const float* grep_w, const float* grep_b, const float* grep_a,
                          float* out, int B, int T, int H, int head_dim, void* stream);
+
+/* The single-product twin of the matrix-core kernel: q * (scale log2 e), k, v and the (unnormalised) probabilities each rounded once
+ * to bf16 where they become an MFMA operand; the softmax's running sum takes the unrounded probabilities; the gate (on the unrounded q)
+ * and the bias are unchanged.  The `attn_valu` tuning key does not reach it (the vector-pipe kernel is sed_attention_relpos). */
+int sed_attention_relpos_bf16x1(const float* qkv, const float* relb, const float* grep_w, const float* grep_b, const float* grep_a,
+                                float* out, int B, int T, int H, int head_dim, void* stream);
 
 /* Tuning overrides for tests / sweep tools / A-B runs (no reference counterpart).  value 0 restores the built-in choice.  Keys:
  *   0  persistent-grid cap of the wide GLU kernels            1  128-channel GLU backward: 1 = 32x32x16 split tiling, 3 = exact f32

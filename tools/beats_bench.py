@@ -1,5 +1,6 @@
 """Throughput of the frozen BEATs extractor at the recipe's size: 48 clips of 10 s -> (48, 768, 496) embeddings,
-iter3 configuration (12 layers), random weights.  Secondary workload: not the headline metric of bench.py."""
+iter3 configuration (12 layers), random weights.  Secondary workload: not the headline metric of bench.py.
+The arithmetic mode comes from the environment variable SED_BEATS_PRECISION ("bf16x3", the default, or "bf16": one MFMA per product)."""
 import json, sys, time
 sys.path.insert(0, ".")
 import torch
@@ -23,13 +24,16 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 48
 if len(sys.argv) > 2:                   # A/B: another build of the C-ABI library (tools/_libsed_*.so)
     _lib.use_library(sys.argv[2], is_emulator=False)
 torch.manual_seed(0)
-model = BEATs(BEATsConfig(CFG)).cuda().eval()
+model = BEATs(BEATsConfig(CFG)).cuda().eval()           # (reads SED_BEATS_PRECISION; anything but the two modes raises)
+MODE = model.precision
+print("[beats_bench] precision:", MODE, flush=True)
 audio = 0.1 * torch.randn(B, 160000, device="cuda")
 for _ in range(2):
     feats, _ = model.extract_features(audio)
 torch.cuda.synchronize()
 lib = _lib.get(); orig = lib.call; rec = {}; work = {}
-PEAK_BF16X3, PEAK_HBM = 2500.0 / 3.0, 8000.0        # TFLOP/s of algorithmic products at three bf16 MFMAs each; GB/s
+PEAK_BF16X3, PEAK_BF16, PEAK_HBM = 2500.0 / 3.0, 2500.0, 8000.0     # TFLOP/s of algorithmic products at three bf16 MFMAs each / at one; GB/s
+PEAK_MFMA = PEAK_BF16 if MODE == "bf16" else PEAK_BF16X3
 
 
 def entry_work(name, a):
@@ -37,7 +41,7 @@ def entry_work(name, a):
     if name.startswith("sed_linear"):
         M, N, K = a[4:7]
         return "mfma", 2.0 * M * N * K
-    if name == "sed_attention_relpos":
+    if name.startswith("sed_attention_relpos"):
         B_, T, H, Dh = a[6:10]
         return "mfma", 4.0 * B_ * H * T * T * Dh
     if name.startswith("sed_posconv"):
@@ -46,7 +50,7 @@ def entry_work(name, a):
     if name == "sed_layernorm":
         M, D = a[6:8]
         return "hbm", 4.0 * M * D * (3 if a[1] else 2)
-    if name == "sed_layernorm_tiles":
+    if name.startswith("sed_layernorm_tiles"):
         M, D = a[8:10]
         return "hbm", 4.0 * M * D * (3 + (1 if a[1] else 0) + (1 if a[2] else 0))
     if name == "sed_kaldi_fbank":
@@ -78,13 +82,14 @@ per = {k: round(sum(a.elapsed_time(b) for a, b in v), 3) for k, v in rec.items()
 roof = {}
 for k, (bound, w) in work.items():
     ach = w / (per[k] * 1e-3) / (1e12 if bound == "mfma" else 1e9)
-    peak = PEAK_BF16X3 if bound == "mfma" else PEAK_HBM
+    peak = PEAK_MFMA if bound == "mfma" else PEAK_HBM
     roof[k] = {"bound": bound, "launches": len(rec[k]), "ms": per[k], "achieved": round(ach, 1), "peak": round(peak, 1),
                "unit": "TFLOP/s" if bound == "mfma" else "GB/s", "frac": round(ach / peak, 4)}
 flops = B * (496 * (2 * 256 * 512 + 2 * 512 * 768) + 12 * (496 * 2 * 768 * (3 * 768 + 768 + 2 * 3072) + 2 * 2 * 12 * 496 * 496 * 64) + 496 * 768 * 2 * 48 * 128)
-print(json.dumps({"workload": "BEATs iter3 extractor, %d clips of 10 s -> (%d, 768, 496)" % (B, B), "ms_per_batch": round(dt * 1e3, 2),
+print(json.dumps({"workload": "BEATs iter3 extractor, %d clips of 10 s -> (%d, 768, 496)" % (B, B), "precision": MODE, "ms_per_batch": round(dt * 1e3, 2),
                   "clips_per_s": round(B / dt, 1), "tflops_algorithmic": round(flops / dt / 1e12, 1), "ms_by_entry": per,
                   "roofline_by_entry": roof,
                   "roofline_note": "HIP events around every launch of one extractor pass; mfma entries: algorithmic FLOPs against 2500/3 = 833 "
-                                   "TFLOP/s (split-bf16: three bf16 MFMAs per fp32-accurate product); hbm entries: algorithmic bytes against 8 TB/s",
+                                   "TFLOP/s (split-bf16: three bf16 MFMAs per fp32-accurate product; 2500 TFLOP/s under precision bf16: one "
+                                   "MFMA per product); hbm entries: algorithmic bytes against 8 TB/s",
                   "finite": bool(torch.isfinite(feats).all())}))
