@@ -10,7 +10,8 @@ frozen: `pretrained.freezed: True`); the modules below HOLD the parameters under
 checkpoints load unchanged, they never run torch arithmetic.
 
 Not built: padding masks, `layer_norm_first` checkpoints, the fine-tuned predictor head, training of the extractor
-(`pretrained.e2e`) -- they raise.
+(`pretrained.freezed: False`) -- they raise.  The frozen extractor inside the training step (`pretrained.e2e: True`) is
+sed_trainer_pretrained.SEDTask4(..., pretrained_model=BEATsModel(...)): `BEATsModel.embeddings(x, "frame")`.
 
 Arithmetic modes (`BEATs.set_precision`, `BEATsModel(..., precision=)`, environment variable SED_BEATS_PRECISION): "bf16x3" (default) = every
 product as three bf16 MFMAs on split operands, fp32-level accuracy; "bf16" = both operands of every contraction rounded once to bf16, one
@@ -286,12 +287,27 @@ class BEATs(nn.Module):
         return self.fbank(source, fbank_mean, fbank_std)
 
     @torch.no_grad()
-    def extract_features(self, source, padding_mask=None, fbank_mean=15.41663, fbank_std=6.55582, taps=None):
-        """taps: optional dict that receives the encoder input and every layer's output (tests / diagnostics)."""
+    def host_draws(self):
+        """The reference encoder draws `np.random.random()` once per layer on EVERY forward -- the LayerDrop coin, which eval mode
+        ignores but still tosses (backbone.py:139-140).  A trainer that runs the extractor in front of its mixup draws
+        (sed_trainer_pretrained.py:305-330) therefore sees a shifted numpy stream; the same draws are made here."""
+        for _ in self.encoder.layers:
+            np.random.random()
+
+    def extract_features(self, source, padding_mask=None, fbank_mean=15.41663, fbank_std=6.55582, taps=None, host_draws=True):
+        """taps: optional dict that receives the encoder input and every layer's output (tests / diagnostics).
+        host_draws: make the reference's per-layer numpy draws (`host_draws()`); False when the caller makes them itself, at the
+        point of its own host-draw order where the reference's forward would have run.
+
+        Capturable into a hipGraph after ONE eager call at the same shape, precision and device: that call builds everything that is
+        built lazily (`_pack`, the weight images, the position-convolution planes, `_rel_bias`, the zero-filled activation images, the
+        fbank tables on the device); every later call allocates through torch.empty only."""
         if padding_mask is not None:
             raise NotImplementedError("padding masks are not built (the recipes extract embeddings of fixed 10 s clips)")
         if self.training and (self.cfg.dropout > 0 or self.cfg.encoder_layerdrop > 0 or self.cfg.attention_dropout > 0):
             raise NotImplementedError("the BEATs extractor is an inference path: call .eval() (pretrained.freezed)")
+        if host_draws:
+            self.host_draws()
         lib = _lib.get()
         cfg = self.cfg
         pk = self._pack()
@@ -448,3 +464,12 @@ class BEATsModel(nn.Module):
     def forward(self, x):
         features = self.model.extract_features(x)[0]
         return {"global": features.mean(dim=1).float(), "frame": features.transpose(1, 2).float()}
+
+    def embeddings(self, x, kind="frame", host_draws=True):
+        """One entry of forward()'s dict, computing only that one.  "frame": the (B, D, tokens) VIEW of the encoder's token-major
+        (B, tokens, D) output -- no mean, no copy (ops.EmbCatFn reads it where it lies); "global": the mean over the tokens.
+        host_draws: see BEATs.extract_features."""
+        if kind not in ("frame", "global"):
+            raise ValueError("embedding kind %r: BEATsModel produces 'frame' and 'global'" % (kind,))
+        features = self.model.extract_features(x, host_draws=host_draws)[0]
+        return features.transpose(1, 2) if kind == "frame" else features.mean(dim=1)

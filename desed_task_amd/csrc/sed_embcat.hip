@@ -102,6 +102,101 @@ SED_API int sed_embcat_fwd(const float* x, const float* emb, float* z, int B, in
     return sed_check_launch();
 }
 
+// ---- token-major twin: the extractor's own layout ---------------------------------------------------------------------------
+// tok (B, Te, E) -- the BEATs encoder's output, one token per row, contiguous along E -- instead of emb (B, E, Te).  A pooling
+// window is then a run of whole rows: a lane adds the same four channels of the window's rows (16-byte loads along E, ascending
+// token order, divided by the count: the arithmetic of embcat_fwd_kernel, bit for bit) and writes them to the output row; no LDS,
+// no transposition.  HBM-bound like its twin: same algorithmic bytes, overlapping windows re-read their shared row from L2.
+#define EMBT_TCH 4         // output frames per workgroup: 4 x E / 4 vector items (768: three per lane)
+
+__device__ __forceinline__ void embt_window(int t, int T, int Te, int mode, int& w0, int& w1) {
+    if (mode == 1) {
+        int src = (int)(((long long)(2 * t + 1) * Te) / (2 * T));
+        w0 = min(src, Te - 1);
+        w1 = w0 + 1;
+    } else {
+        w0 = emb_win_lo(t, Te, T);
+        w1 = emb_win_hi(t, Te, T);
+    }
+}
+
+__global__ __launch_bounds__(EMB_THREADS) void embcat_tokens_fwd_kernel(const float* __restrict__ x, const float* __restrict__ tok,
+                                                                         float* __restrict__ z, int T, int Te, int C, int E, int vec,
+                                                                         uint32_t seed, uint32_t thr24, float dscale,
+                                                                         const unsigned* __restrict__ seed_dev,
+                                                                         const int* __restrict__ tmask, int mode) {
+    if (seed_dev) seed += *seed_dev;
+    const int nchunk = (T + EMBT_TCH - 1) / EMBT_TCH;      // flat grid: B * nchunk <= B * T < 2^31
+    const int b = blockIdx.x / nchunk, tid = threadIdx.x;
+    const int t0 = (blockIdx.x % nchunk) * EMBT_TCH, t1 = min(T, t0 + EMBT_TCH), W = C + E;
+    int mx0 = 0, mx1 = 0, me0 = 0, me1 = 0;
+    if (tmask) { mx0 = tmask[4 * b]; mx1 = tmask[4 * b + 1]; me0 = tmask[4 * b + 2]; me1 = tmask[4 * b + 3]; }
+    const size_t m0 = (size_t)b * T + t0;
+    {                                           // the x columns of these frames, as in the twin
+        const float* xs = x + m0 * C;
+        const int n = (t1 - t0) * C, dt = EMB_THREADS / C, dc = EMB_THREADS % C;
+        int t = tid / C, c = tid % C;
+        for (int i = tid; i < n; i += EMB_THREADS) {
+            const size_t o = (m0 + t) * W + c;
+            const bool gone = (t0 + t) >= mx0 && (t0 + t) < mx1;
+            z[o] = (!gone && sed_keep((uint32_t)o, seed, thr24)) ? xs[i] * dscale : 0.f;
+            t += dt; c += dc;
+            if (c >= C) { c -= C; ++t; }
+        }
+    }
+    const float* src = tok + (size_t)b * Te * E;
+    if (vec) {                                  // E % 4 == 0 and tok 16-byte aligned: every row starts on a 16-byte boundary
+        const int E4 = E >> 2, n = (t1 - t0) * E4;
+        for (int i = tid; i < n; i += EMB_THREADS) {
+            const int t = t0 + i / E4, e = (i % E4) << 2;
+            int w0, w1;
+            embt_window(t, T, Te, mode, w0, w1);
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+            for (int s = w0; s < w1; ++s) {
+                const float4 r = *(const float4*)(src + (size_t)s * E + e);
+                a0 += r.x; a1 += r.y; a2 += r.z; a3 += r.w;
+            }
+            const float cnt = (float)(w1 - w0);
+            const size_t o = ((size_t)b * T + t) * W + C + e;
+            const bool gone = t >= me0 && t < me1;
+            float4 v;
+            v.x = (!gone && sed_keep((uint32_t)o, seed, thr24)) ? (a0 / cnt) * dscale : 0.f;
+            v.y = (!gone && sed_keep((uint32_t)(o + 1), seed, thr24)) ? (a1 / cnt) * dscale : 0.f;
+            v.z = (!gone && sed_keep((uint32_t)(o + 2), seed, thr24)) ? (a2 / cnt) * dscale : 0.f;
+            v.w = (!gone && sed_keep((uint32_t)(o + 3), seed, thr24)) ? (a3 / cnt) * dscale : 0.f;
+            float* dst = z + o;
+            if ((((uintptr_t)dst) & 15) == 0) *(float4*)dst = v;
+            else { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; dst[3] = v.w; }
+        }
+        return;
+    }
+    const int n = (t1 - t0) * E;
+    for (int i = tid; i < n; i += EMB_THREADS) {
+        const int t = t0 + i / E, e = i % E;
+        int w0, w1;
+        embt_window(t, T, Te, mode, w0, w1);
+        float acc = 0.f;
+        for (int s = w0; s < w1; ++s) acc += src[(size_t)s * E + e];
+        const float v = acc / (float)(w1 - w0);
+        const size_t o = ((size_t)b * T + t) * W + C + e;
+        z[o] = (!(t >= me0 && t < me1) && sed_keep((uint32_t)o, seed, thr24)) ? v * dscale : 0.f;
+    }
+}
+
+// x (B,T,C), tok (B,Te,E) -> z (B,T,C+E): sed_embcat_fwd on the transposed embeddings, bit for bit.
+SED_API int sed_embcat_tokens_fwd(const float* x, const float* tok, float* z, int B, int T, int Te, int C, int E, unsigned seed,
+                                     unsigned thr24, float dscale, const unsigned* seed_dev, const int* tmask, int mode, void* stream) {
+    if (B <= 0 || T <= 0) return SED_OK;
+    if (Te < 1 || C < 1 || E < 1 || mode < 0 || mode > 1) return SED_ERR_ARG;
+    if ((size_t)B * T * (C + E) >= (1ull << 32) || (long long)(T + 1) * Te + T >= (1ll << 31) || C > (1 << 20))
+        return SED_ERR_UNSUPPORTED;
+    const int vec = (E % 4 == 0 && ((uintptr_t)tok & 15) == 0) ? 1 : 0;
+    const int nchunk = (T + EMBT_TCH - 1) / EMBT_TCH;
+    SED_LAUNCH(embcat_tokens_fwd_kernel, dim3((unsigned)(B * nchunk)), dim3(EMB_THREADS), 0, (hipStream_t)stream, x, tok, z, T, Te, C, E, vec,
+               seed, thr24, dscale, seed_dev, tmask, mode);
+    return sed_check_launch();
+}
+
 __global__ __launch_bounds__(256) void embcat_bwd_kernel(const float* __restrict__ dzx, float* __restrict__ dx, size_t n, int C,
                                                           int W, uint32_t seed, uint32_t thr24, float dscale,
                                                           const unsigned* __restrict__ seed_dev, const int* __restrict__ tmask, int T) {

@@ -239,7 +239,9 @@ class GraphedStepDriver:
 
     The first `warmup` steps run eagerly (they are ordinary training steps and let the allocator, the lazily built
     buffers and hipFuncSetAttribute calls settle); the next step is captured; every later step re-runs the recorded
-    host half, uploads DynArgs, copies the batch into the static input buffers and replays.
+    host half, uploads DynArgs, copies the batch into the static input buffers and replays.  (A pipelined replay skips the
+    waveforms, whose features the previous replay prefetched -- unless the task sets `step_reads_waveforms`, as the e2e
+    pretrained step does for its extractor: then they are copied into `input_buffers()[0]` before every replay.)
 
     Every step -- eager warm-up, capture, replay -- runs on the driver's OWN stream: autograd's AccumulateGrad nodes are
     bound to the stream of the first backward and live as long as the parameters, and a node bound to the legacy default
@@ -488,8 +490,9 @@ class GraphedStepDriver:
                 if st is not None:
                     if not torch.is_tensor(t) or t.shape != st.shape:
                         raise ValueError("batch tensor shapes changed after the step was captured")
-                    if pipelined and st is self.static[0]:
+                    if pipelined and st is self.static[0] and not getattr(task, "step_reads_waveforms", False):
                         continue                            # the graph reads this batch's FEATURES (prefetched), not its waveforms
+                                                            # (unless the step runs an extractor on them: pretrained.e2e)
                     if teacher_level and any(st is self.static[i] for i in skip if i < len(self.static)):
                         continue                            # ... and its labels (+ the 2024 step's embeddings) as the previous
                                                             # replay's side branch left them in the hand-over buffers

@@ -196,7 +196,7 @@ class CRNN(nn.Module):
             if embeddings is None:
                 raise ValueError("this CRNN was built with use_embeddings=True: forward() needs embeddings")
             if embeddings.requires_grad:
-                raise NotImplementedError("embeddings are frozen features here (pretrained.e2e / unfrozen extractors are not built)")
+                raise NotImplementedError("embeddings are frozen features here (unfrozen extractors, pretrained.freezed: False, are not built)")
             tmask = None
             if dropstep:        # two independent TimeMasking draws: the CNN features first, then the embeddings (:292-293)
                 bx, be = self._dropstep_bounds(B, Tp, h.device), self._dropstep_bounds(B, Tp, h.device)

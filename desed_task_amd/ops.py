@@ -649,17 +649,23 @@ class BiGRULayerFn(torch.autograd.Function):
 
 class EmbCatFn(torch.autograd.Function):
     """Embedding fusion of CRNN.py:283-296 (aggregation_type "pool1d"): cat_tf(dropout(cat(x, pool1d(emb)))).
-    x (B,T,C), emb (B,E,Te) frozen features -> (B,T,C).  One fused pooling/concat/dropout kernel (K14) + the K7 GEMMs."""
+    x (B,T,C), emb (B,E,Te) frozen features -> (B,T,C).  One fused pooling/concat/dropout kernel (K14: sed_embcat_fwd on dense
+    (B,E,Te) storage, sed_embcat_tokens_fwd on the transposed view of (B,Te,E) storage) + the K7 GEMMs."""
 
     @staticmethod
     def forward(ctx, x, emb, w, b, cfg):
         lib = _lib.get()
-        x, emb, w = x.contiguous(), emb.contiguous().float(), w.contiguous()
-        _lib.check_tensor(x, "embcat input")
-        _lib.check_tensor(emb, "embeddings")
+        x, w = x.contiguous(), w.contiguous()
         B, T, C = x.shape
         if emb.dim() != 3 or emb.shape[0] != B:
             raise ValueError("embeddings must be (batch, embedding_size, frames)")
+        # the (B, E, Te) VIEW of token-major storage (B, Te, E) -- what beats.BEATsModel returns as "frame", and a clone() of it --
+        # is read where it lies by the token-major kernel (same z, bit for bit); every other layout is made dense (B, E, Te) first
+        tokens = emb.dtype == torch.float32 and not emb.is_contiguous() and emb.transpose(1, 2).is_contiguous()
+        if not tokens:
+            emb = emb.contiguous().float()
+        _lib.check_tensor(x, "embcat input")
+        _lib.check_tensor(emb.transpose(1, 2) if tokens else emb, "embeddings")
         E, Te = emb.shape[1], emb.shape[2]
         if w.shape != (C, C + E):
             raise ValueError(f"cat_tf.weight is {tuple(w.shape)}, expected {(C, C + E)}")
@@ -670,8 +676,8 @@ class EmbCatFn(torch.autograd.Function):
         f32 = dict(device=x.device, dtype=torch.float32)
         z = torch.empty(B, T, C + E, **f32)
         tmask, mode = cfg.get("tmask"), int(cfg.get("mode", 0))       # dropstep_recurrent bounds (B,4) int32; 1 = "interpolate"
-        lib.call("sed_embcat_fwd", x.data_ptr(), emb.data_ptr(), z.data_ptr(), B, T, Te, C, E, int(seed), thr24, dscale,
-                 _graph.seed_dev(seed), _p(tmask), mode, st)
+        lib.call("sed_embcat_tokens_fwd" if tokens else "sed_embcat_fwd", x.data_ptr(), emb.data_ptr(), z.data_ptr(), B, T, Te, C, E,
+                 int(seed), thr24, dscale, _graph.seed_dev(seed), _p(tmask), mode, st)
         y = torch.empty(B, T, C, **f32)
         lib.call(gemm_entry(cfg, pair=False), z.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(), B * T, C, C + E, C + E, C + E, C,
                  0, 1, 1, 0, st)

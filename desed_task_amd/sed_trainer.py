@@ -224,6 +224,10 @@ class SEDTask4(_Base):
             return "student / teacher are not desed_task_amd.nnet.CRNN"
         if not isinstance(self.opt, FusedAdam) or self.scheduler is None:
             return "the optimizer is not a plain Adam over sed_student.parameters() (arena.FusedAdam.adopt), or there is no scheduler"
+        if getattr(self, "_e2e", False):
+            from .beats import BEATsModel
+            if not isinstance(getattr(self, "pretrained_model", None), BEATsModel):
+                return "pretrained.e2e: the extractor is not a desed_task_amd.beats.BEATsModel (a foreign extractor runs the eager step)"
         if tr.get("accumulate_batches", 1) != 1:
             return "accumulate_batches != 1 (one optimizer step per training_step is what a whole step is)"
         # (gradient_clip > 0 is no blocker: the driver hands it to the adopted FusedAdam, which clips inside its own launches)

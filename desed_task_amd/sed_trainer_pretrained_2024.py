@@ -24,7 +24,7 @@ sed_eval_metrics.EventBasedMetrics.  The codecarbon energy keys are not produced
 Class names: `class_labels={"desed": ..., "maestro_real": ..., "maestro_real_eval": ...}` given to the constructor or as
 hparams["class_labels"]; else the recipe's own `local.classes_dict` (reachable when the recipe directory is on the path).
 
-Not built: `pretrained.e2e`.  The recipe's own `net:` section (n_RNN_cell 192, 27 classes, dropstep_recurrent) is what the parity
+Not built: `pretrained.e2e` in this (2024) trainer -- it raises, as the reference's does (:305-309).  The recipe's own `net:` section (n_RNN_cell 192, 27 classes, dropstep_recurrent) is what the parity
 fixtures use.
 """
 import os

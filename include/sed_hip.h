@@ -403,6 +403,14 @@ int sed_segment_scores(const float* scores, const float* clip_len, float* out, i
  * (aggregation_type "pool1d"), 1 = nearest-exact interpolation (aggregation_type "interpolate", :271-279). */
 int sed_embcat_fwd(const float* x, const float* emb, float* z, int B, int T, int Te, int C, int E, unsigned seed,
                    unsigned thr24, float dscale, const unsigned* seed_dev, const int* tmask, int mode, void* stream);
+/* The same z from TOKEN-MAJOR embeddings tok (B,Te,E), contiguous along E: the layout the BEATs encoder leaves them in
+ * (local/beats/BEATs.py:205-223 returns their transposed view as "frame"; sed_trainer_pretrained.py:291-312 hands it to
+ * CRNN.py:283-296 when pretrained.e2e is on).  Every other argument as in sed_embcat_fwd; the window is summed in ascending token
+ * order and divided by its length, so that z is bit-identical to sed_embcat_fwd on the transposed copy.  Rows are read as 16-byte
+ * words when E % 4 == 0 and tok is 16-byte aligned, else element-wise.  Same SED_ERR_ARG / SED_ERR_UNSUPPORTED limits (no LDS bound).
+ * The backward is sed_embcat_bwd (it does not read the embeddings). */
+int sed_embcat_tokens_fwd(const float* x, const float* tok, float* z, int B, int T, int Te, int C, int E, unsigned seed,
+                          unsigned thr24, float dscale, const unsigned* seed_dev, const int* tmask, int mode, void* stream);
 /* dx (M,C) = dzx (M,C) masked/scaled with the forward's dropout mask; dzx = the first C columns of dz = dy . W_cat_tf. */
 int sed_embcat_bwd(const float* dzx, float* dx, int M, int C, int E, unsigned seed, unsigned thr24, float dscale,
                    const unsigned* seed_dev, const int* tmask, int T, void* stream);
