@@ -588,10 +588,13 @@ def _seed_all(seed, rank):
     _ops.reseed_dropout()
 
 
-def build_run(config, log_dir, rank=0, world=1, strong_real=False, fast_dev_run=False, test_only=False, evaluation=False):
+def build_run(config, log_dir, rank=0, world=1, strong_real=False, fast_dev_run=False, test_only=False, evaluation=False,
+              resident_device=None, log=None):
     """train_sed.py:79-246 -> the SEDTask4 of this package with the reference's data objects (imported from the reference checkout on
     PYTHONPATH; nothing of them is re-implemented here).  The train sampler is the recipe's ConcatDatasetBatchSampler seen through
-    RankShardedBatchSampler: rank r trains on batches r, r + world, ... of every epoch."""
+    RankShardedBatchSampler: rank r trains on batches r, r + world, ... of every epoch.
+    resident_device: read the training and validation sets ONCE into pools on that device (resident.py; every rank holds the whole
+    pool) -- `train_data` / `valid_data` then hand out batches gathered on the device, the sampler is the same one."""
     import pandas as pd
     try:
         from desed_task.dataio import ConcatDatasetBatchSampler
@@ -638,9 +641,19 @@ def build_run(config, log_dir, rank=0, world=1, strong_real=False, fast_dev_run=
     steps_per_epoch = min(len(p) // (b * tr["accumulate_batches"]) for p, b in zip(parts, tr["batch_size"])) // world
     opt = torch.optim.Adam(student.parameters(), config["opt"]["lr"], betas=(0.9, 0.999))
     scheduler = {"scheduler": ExponentialWarmup(opt, config["opt"]["lr"], tr["n_epochs_warmup"] * max(steps_per_epoch, 1)), "interval": "step"}
-    return SEDTask4(config, encoder=encoder, sed_student=student, opt=opt, train_data=torch.utils.data.ConcatDataset(parts),
-                    valid_data=torch.utils.data.ConcatDataset([synth_val, weak_val]), test_data=test_data, train_sampler=sampler,
-                    scheduler=scheduler, fast_dev_run=fast_dev_run, evaluation=evaluation)
+    train_data, valid_data = torch.utils.data.ConcatDataset(parts), torch.utils.data.ConcatDataset([synth_val, weak_val])
+    if resident_device is not None:
+        from .resident import ResidentEvalSet, ResidentPool, ResidentTrainSet
+        workers = 1 if fast_dev_run else tr["num_workers"]
+        pool = ResidentPool.from_dataset(train_data, resident_device, num_workers=workers)
+        names = []
+        pool_val = ResidentPool.from_dataset(valid_data, resident_device, num_workers=workers, filenames=names)
+        if log is not None:
+            log("resident data: train %s; validation %s" % (pool.describe(), pool_val.describe()))
+        train_data, sampler = ResidentTrainSet(pool, sampler), None         # (the set owns the sampler: one batch per item)
+        valid_data = ResidentEvalSet(pool_val, tr["batch_size_val"], names)
+    return SEDTask4(config, encoder=encoder, sed_student=student, opt=opt, train_data=train_data, valid_data=valid_data,
+                    test_data=test_data, train_sampler=sampler, scheduler=scheduler, fast_dev_run=fast_dev_run, evaluation=evaluation)
 
 
 def _run_eval(task, loader, device, step, limit):
@@ -673,9 +686,14 @@ def fit(task, device, n_epochs, log_dir, world=1, rank=0, start_epoch=0, limit_t
         driver = GraphedStepDriver(task, world_size=world, prefetch=os.environ.get("SED_PREFETCH", "teacher"))
     else:
         driver = StepDriver(task, world_size=world, prefetch=os.environ.get("SED_PREFETCH", "teacher"))
-    sampler = task.train_sampler
-    # a plain DataLoader over the rank's share (pinned host memory: the upload of batch k + 2 runs beside step k)
-    loader = torch.utils.data.DataLoader(task.train_data, batch_sampler=sampler, num_workers=task.num_workers, pin_memory=device.type == "cuda")
+    resident = task.train_sampler is None and getattr(task.train_data, "yields_batches", False)
+    if resident:
+        # resident.ResidentTrainSet: iterated as it is -- every batch is gathered on the device, nothing to pin, stage or upload
+        loader, sampler = task.train_data, task.train_data.batch_sampler
+    else:
+        sampler = task.train_sampler
+        # a plain DataLoader over the rank's share (pinned host memory: the upload of batch k + 2 runs beside step k)
+        loader = torch.utils.data.DataLoader(task.train_data, batch_sampler=sampler, num_workers=task.num_workers, pin_memory=device.type == "cuda")
     n_train = len(loader) if limit_train_batches is None else min(len(loader), int(limit_train_batches))
     if n_train < 1:
         raise SystemExit("no training batch per rank: %d batches of the sampler / %d ranks" % (len(sampler.batch_sampler), world))
@@ -700,16 +718,18 @@ def fit(task, device, n_epochs, log_dir, world=1, rank=0, start_epoch=0, limit_t
                 if b is None:
                     break
                 ahead.append(b)
-                task._stage((epoch, k + len(ahead)), b, device)
+                if not resident:
+                    task._stage((epoch, k + len(ahead)), b, device)
 
-        cur = move_to_device(next(it), device)
+        cur = next(it) if resident else move_to_device(next(it), device)
         loss = None
         for k in range(n_train):
             pull(k)
             nxt = None
             if ahead:
-                ahead.pop(0)
-                nxt = task._take_staged((epoch, k + 1), device)
+                nxt = ahead.pop(0)
+                if not resident:
+                    nxt = task._take_staged((epoch, k + 1), device)
             loss = driver.run_step(cur, k, next_batch=nxt)
             cur = nxt
             if cur is None:
@@ -798,6 +818,8 @@ def main(argv=None, cpu_test_device=False, entry_module="desed_task_amd.launcher
     ap.add_argument("--eval_from_checkpoint", default=None)
     ap.add_argument("--gpus", default="1", help="number of GPUs of this node (one process each)")
     ap.add_argument("--fast_dev_run", action="store_true")
+    ap.add_argument("--resident_data", action="store_true", help="read the training and validation sets once into device memory and "
+                    "gather every batch there (also: training.resident_data: True)")
     args = ap.parse_args(argv)
     n = int(args.gpus)
     if "RANK" not in os.environ and max(n, 1) > 1:
@@ -829,7 +851,9 @@ def main(argv=None, cpu_test_device=False, entry_module="desed_task_amd.launcher
         if world > 1:
             dist.barrier()
         return 0
-    task = build_run(config, log_dir, rank, world, strong_real=args.strong_real, fast_dev_run=args.fast_dev_run)
+    resident = args.resident_data or bool(config["training"].get("resident_data"))
+    task = build_run(config, log_dir, rank, world, strong_real=args.strong_real, fast_dev_run=args.fast_dev_run,
+                     resident_device=device if resident else None, log=(lambda msg: print(msg, flush=True)) if rank == 0 else None)
     task.to(device)
     if rank == 0:
         clip = config["training"].get("gradient_clip") or 0

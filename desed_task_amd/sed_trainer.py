@@ -176,6 +176,9 @@ class SEDTask4(_Base):
         return self.train_loader
 
     def val_dataloader(self):               # sed_trainer.py:922-930
+        if getattr(self.valid_data, "yields_batches", False):       # ready batches (resident.ResidentEvalSet): iterated as they are
+            self.val_loader = torch.utils.data.DataLoader(self.valid_data, batch_size=None, num_workers=0)
+            return self.val_loader
         self.val_loader = torch.utils.data.DataLoader(self.valid_data, batch_size=self.hparams["training"]["batch_size_val"],
                                                       num_workers=self.num_workers, shuffle=False, drop_last=False)
         return self.val_loader

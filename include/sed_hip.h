@@ -573,6 +573,34 @@ int sed_attention_relpos(const float* qkv, const float* relb, const float* grep_
 int sed_attention_relpos_bf16x1(const float* qkv, const float* relb, const float* grep_w, const float* grep_b, const float* grep_a,
                                 float* out, int B, int T, int H, int head_dim, void* stream);
 
+/* ---- resident training set: batches gathered on the device (desed_task_amd/resident.py) ---------------------------------------------
+ * Replaces, per training step, the reference's host data path: torchaudio.load + label encoding of every item
+ * (desed_task/dataio/datasets.py:60-74,187-237), default_collate and the DataLoader of
+ * recipes/dcase2023_task4_baseline/local/sed_trainer.py:913-920, and the host-to-device copy of the collated batch.  The data set is
+ * read once into device pools, one per stream (waveforms, labels, embeddings, class mask); ONE launch then assembles a batch:
+ *     for every stream s and output row b:   out_s[b, 0:len_s] = convert_s(pool_s[idx[b], 0:len_s]).
+ * desc: n_streams (1 .. SED_GATHER_MAX_STREAMS) descriptors of SED_GATHER_DESC_BYTES bytes each, in DEVICE memory, written once by the
+ * host (little-endian, no padding):
+ *     offset  0  const void* pool     first element of pool row 0; row r starts `stride` input elements further per row
+ *     offset  8  void*       out      dense (n_rows, len) output elements
+ *     offset 16  long long   stride   input elements between pool rows (rows padded to a multiple of 16 bytes)
+ *     offset 24  int         len      elements per row
+ *     offset 28  int         kind     SED_GATHER_I16_TO_F32: float(x) * 2^-15 (exact; what torchaudio.load yields for 16-bit PCM),
+ *                                     SED_GATHER_F32: copy, SED_GATHER_U8_TO_F32: float(x) (0/1 label matrices), SED_GATHER_U8: copy (bool masks)
+ * idx: n_rows int32 pool rows in device memory (a window of the epoch's index table).  THE KERNEL CHECKS NO INDEX: the caller
+ * guarantees 0 <= idx[b] < rows of every pool (resident.py validates every epoch's table on the host before uploading it).
+ * chunks_per_row = sum over the streams of ceil(len / SED_GATHER_CHUNK): a workgroup copies one chunk of one row, so the grid
+ * (n_rows * chunks_per_row) follows the bytes to move.  Rows whose pool and output start are both 16-byte aligned move as 16-byte
+ * words with an element-wise tail, any other row element-wise. */
+#define SED_GATHER_MAX_STREAMS 4
+#define SED_GATHER_DESC_BYTES 32
+#define SED_GATHER_CHUNK 4096
+#define SED_GATHER_I16_TO_F32 0
+#define SED_GATHER_F32 1
+#define SED_GATHER_U8_TO_F32 2
+#define SED_GATHER_U8 3
+int sed_batch_gather(const void* desc, int n_streams, const int* idx, int n_rows, int chunks_per_row, void* stream);
+
 /* Tuning overrides for tests / sweep tools / A-B runs (no reference counterpart).  value 0 restores the built-in choice.  Keys:
  *   0  persistent-grid cap of the wide GLU kernels            1  128-channel GLU backward: 1 = 32x32x16 split tiling, 3 = exact f32
  *   2  channels per weight chunk of the split-bf16 conv       3  pixels per workgroup of the split-bf16 conv
