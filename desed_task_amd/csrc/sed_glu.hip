@@ -2149,6 +2149,9 @@ SED_API int sed_glu_bwd(const float* y, const float* stats, const float* gamma, 
                            const unsigned* seed_dev, int split_bf16, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (F % PF != 0) return SED_ERR_UNSUPPORTED;
+    // a configuration no kernel below is built for is refused before anything is written (the zero-tail and zero-fill launches used to
+    // run first)
+    if (!(PT == 1 && PF == 2 && (C == 64 || C == 128)) && !(PT == 2 && PF == 2 && (C == 16 || C == 32))) return SED_ERR_UNSUPPORTED;
     if (PT == 1 && PF == 2) {
         // C = 128, split-bf16: the 16x16x32 kernel (glu128_bwd_c_kernel; 87 us at B = 48, F = 16 against 174 us of the exact-f32
         // kernel and 204 us of the 32x32x16 tiling, whose two fragment sets of 128 VGPRs spill).
@@ -2160,7 +2163,7 @@ SED_API int sed_glu_bwd(const float* y, const float* stats, const float* gamma, 
         if (C == 64) return launch_glu_wide_bwd<64, false>(y, stats, gamma, beta, Wg, bg, gout, dz, dWg, dbg, dgamma, dbeta, scratch, B, T, F, seed, thr24, dscale, seed_dev, s);
     }
     const bool lds_free32 = C == 32 && PT == 2 && PF == 2 && F % 16 == 0 && T >= 2;      // glu32_bwd_kernel zeroes the dropped frame itself
-    if (T % PT != 0 && !lds_free32) {
+    if (T % PT != 0 && !lds_free32 && B > 0) {                 // (B = 0: an empty grid is a launch error that the next entry would report)
         // frames the floor-mode pooling drops get no gradient: zero just those rows (zeroing all of dz was a 123 MB memset
         // per step for block 1)
         const int tail = T % PT, rowf4 = F * C / 4;
