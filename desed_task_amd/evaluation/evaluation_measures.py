@@ -142,16 +142,32 @@ def compute_psds_from_operating_points(prediction_dfs, ground_truth_file, durati
 
 
 def compute_psds_from_scores(scores, ground_truth_file, durations_file, dtc_threshold=0.5, gtc_threshold=0.5,
-                             cttc_threshold=0.3, alpha_ct=0, alpha_st=0, max_efpr=100, num_jobs=4, save_dir=None):
+                             cttc_threshold=0.3, alpha_ct=0, alpha_st=0, max_efpr=100, num_jobs=4, save_dir=None, classes=None,
+                             tables=None):
     """Threshold-free PSDS of the score tables `scores` ({audio_id: DataFrame}) (evaluation_measures.py:258-304).  The ground
     truth / durations may be the dicts of `read_ground_truth_events` / `read_audio_durations` (as the reference passes them)
     or TSV paths.  Computed by psds_scores.psds_from_scores -- an exact all-thresholds PSD-ROC with psds.py's criteria, NOT a
     restatement of sed_scores_eval's code (parity with that package unpinned, see psds_scores.py).  `num_jobs` is accepted and
-    unused; with `save_dir` the score tables and the PSD-ROC are written as TSV files."""
+    unused; with `save_dir` the score tables and the PSD-ROC are written as TSV files.
+
+    `scores` may also be a psds_device.ScoreBuffer (scores kept on the device): the per-clip work then runs in the
+    `sed_psds_steps` kernel (psds_device.psds_from_score_buffer), `classes` selects score columns by name, and with `save_dir` the
+    tables written are `tables`, or the buffer's `to_tables()` when none are given."""
+    from .psds_device import ScoreBuffer, psds_from_score_buffer
     from .psds_scores import psds_from_scores, read_audio_durations, read_ground_truth_events, write_psd_roc
-    psds, _, psd_roc, _ = psds_from_scores(scores, read_ground_truth_events(ground_truth_file), read_audio_durations(durations_file),
-                                           dtc_threshold=dtc_threshold, gtc_threshold=gtc_threshold, cttc_threshold=cttc_threshold,
-                                           alpha_ct=alpha_ct, alpha_st=alpha_st, max_efpr=max_efpr)
+    if isinstance(scores, ScoreBuffer):
+        psds, _, psd_roc, _ = psds_from_score_buffer(
+            scores, read_ground_truth_events(ground_truth_file), read_audio_durations(durations_file), dtc_threshold=dtc_threshold,
+            gtc_threshold=gtc_threshold, cttc_threshold=cttc_threshold, alpha_ct=alpha_ct, alpha_st=alpha_st, max_efpr=max_efpr,
+            classes=classes)
+        if save_dir is not None:
+            scores = tables if tables is not None else scores.to_tables()
+    else:
+        if classes is not None or tables is not None:
+            raise ValueError("`classes` / `tables` go with a ScoreBuffer; score tables are selected by their columns")
+        psds, _, psd_roc, _ = psds_from_scores(scores, read_ground_truth_events(ground_truth_file), read_audio_durations(durations_file),
+                                               dtc_threshold=dtc_threshold, gtc_threshold=gtc_threshold, cttc_threshold=cttc_threshold,
+                                               alpha_ct=alpha_ct, alpha_st=alpha_st, max_efpr=max_efpr)
     if save_dir is not None:
         from ..postprocess import write_sed_scores
         write_sed_scores(scores, os.path.join(save_dir, "scores"))

@@ -164,8 +164,7 @@ def psds_from_scores(scores, ground_truth, audio_durations, dtc_threshold=0.5, g
                 dct_l[c].append(full)
     if total_dur <= 0:
         raise ValueError("the evaluated clips have no duration")
-    rocs = {}
-    for c in range(nc):
+    def class_counts(c):
         thr = np.concatenate(thr_l[c])
         order = np.argsort(thr, kind="stable")
         thr = thr[order]
@@ -174,12 +173,28 @@ def psds_from_scores(scores, ground_truth, audio_durations, dtc_threshold=0.5, g
         last = np.concatenate((thr[1:] != thr[:-1], [True]))         # the operating point after ALL jumps at a score value
         tp = np.concatenate(([base_tp[c]], tp[last]))
         fp = np.concatenate(([base_fp[c]], fp[last]))
+        ctc = None
+        if use_ct:
+            ctc = base_ct[c][None, :] + np.cumsum(np.concatenate(dct_l[c])[order], 0)
+            ctc = np.concatenate((base_ct[c][None, :], ctc[last]))
+        return tp, fp, ctc
+
+    return _psd_roc_tail(classes, class_counts, n_gt, gt_dur, total_dur, nsec, use_ct, alpha_ct, alpha_st, max_efpr)
+
+
+def _psd_roc_tail(classes, class_counts, n_gt, gt_dur, total_dur, nsec, use_ct, alpha_ct, alpha_st, max_efpr):
+    """From data-set level counts to the result of `psds_from_scores`: shared by the host path above and the device path
+    (psds_device.psds_from_score_buffer).  class_counts(c) -> (tp, fp, ctc): the counts of class c at every operating point, row 0 =
+    threshold below all scores, then one row per distinct score value ascending (float64; ctc (rows, classes), None without cross
+    triggers)."""
+    nc = len(classes)
+    rocs = {}
+    for c in range(nc):
+        tp, fp, ctc = class_counts(c)
         with np.errstate(divide="ignore", invalid="ignore"):
             tpr = tp / n_gt[c]
             efpr = fp * nsec / total_dur
             if use_ct:
-                ctc = base_ct[c][None, :] + np.cumsum(np.concatenate(dct_l[c])[order], 0)
-                ctc = np.concatenate((base_ct[c][None, :], ctc[last]))
                 ctr = ctc * nsec / gt_dur[None, :]
                 ctr[:, c] = 0.0
                 efpr = efpr + alpha_ct * PSDSEval._mean_ctr(ctr[:, :, None])[:, 0]

@@ -149,15 +149,22 @@ def _filter_batch(scores, median_filter):
     return torch.from_numpy(filt).to(scores.device)
 
 
-def batched_decode_preds(strong_preds, filenames, encoder, thresholds=[0.5], median_filter=7, pad_indx=None):  # noqa: B006
+def batched_decode_preds(strong_preds, filenames, encoder, thresholds=[0.5], median_filter=7, pad_indx=None,  # noqa: B006
+                         device_scores=None):
     """Reference signature and return value (utils.py:16-73); `median_filter` is the window length as there, or (2024 recipe)
     None / a ClassWiseMedianFilter / any callable on a clip's (frames, classes) array.  `thresholds=[]` (the 2024 validation)
     returns the score tables and an empty dict of decodings.
 
     Knowing deviation: with `pad_indx` the reference crops `c_scores[:true_len]` BEFORE transposing, i.e. along the class axis
     of the (NC, T) tensor (utils.py:48-52) -- an inert slip, since no caller of the 2023 recipe passes `pad_indx`.  Here
-    `pad_indx` crops the time axis, which is what the argument documents."""
+    `pad_indx` crops the time axis, which is what the argument documents.
+
+    `device_scores` (an evaluation.psds_device.ScoreBuffer): the filtered scores are appended there and stay on the device; the two
+    score-table dicts come back empty -- neither the tables nor the two host copies that feed them are made.  One clip length per
+    buffer, so not together with `pad_indx`."""
     import pandas as pd
+    if device_scores is not None and pad_indx is not None:
+        raise ValueError("device_scores keeps clips of one length: it cannot be combined with pad_indx")
     scores = _btc(strong_preds)                                   # (B, T, NC)
     B, T, NC = scores.shape
     true_len = None
@@ -176,14 +183,17 @@ def batched_decode_preds(strong_preds, filenames, encoder, thresholds=[0.5], med
         counts, events = np.zeros((0, B, NC), dtype=np.int32), np.zeros((0, B, NC, 1, 2), dtype=np.int32)
     else:
         counts, events = threshold_events(filt, thresholds, true_len)
-    raw_np, filt_np = scores.cpu().numpy(), filt.cpu().numpy()
     scores_raw, scores_post = {}, {}
     audio_ids = [Path(f).stem for f in filenames]
-    for j in range(B):
-        n = T if true_len is None else true_len[j]
-        ts = encoder._frame_to_time(np.arange(n + 1))
-        scores_raw[audio_ids[j]] = create_score_dataframe(raw_np[j, :n], ts, encoder.labels)
-        scores_post[audio_ids[j]] = create_score_dataframe(filt_np[j, :n], ts, encoder.labels)
+    if device_scores is not None:
+        device_scores.append(filt, audio_ids, timestamps=encoder._frame_to_time(np.arange(T + 1)), event_classes=encoder.labels)
+    else:
+        raw_np, filt_np = scores.cpu().numpy(), filt.cpu().numpy()
+        for j in range(B):
+            n = T if true_len is None else true_len[j]
+            ts = encoder._frame_to_time(np.arange(n + 1))
+            scores_raw[audio_ids[j]] = create_score_dataframe(raw_np[j, :n], ts, encoder.labels)
+            scores_post[audio_ids[j]] = create_score_dataframe(filt_np[j, :n], ts, encoder.labels)
     # all regions of all thresholds at once; np.nonzero walks (threshold, clip, class, region) in C order, which is the
     # reference's row order per threshold: clip-major, then decode_strong's class-major / time order
     valid = np.arange(events.shape[3])[None, None, None, :] < counts[..., None]

@@ -800,6 +800,23 @@ class SEDTask4(_Base):
             self.val_scores_postprocessed_buffer_teacher_synth = {}
             self.get_weak_student_f1_seg_macro = SEDTask4._MacroF1()
             self.get_weak_teacher_f1_seg_macro = SEDTask4._MacroF1()
+        if not hasattr(self, "val_scores_device_buffer_student"):
+            self._reset_device_scores("val")
+
+    def _device_psds(self):
+        """`training.device_psds: True` (default off): the post-processed scores stay on the device in ScoreBuffers and the
+        threshold-free PSDS is computed there (evaluation/psds_device.py) instead of from per-clip pandas tables.  `evaluation=True`
+        only writes tables and keeps the host path."""
+        return bool(self.hparams["training"].get("device_psds", False)) and not self.evaluation
+
+    def _reset_device_scores(self, stage):
+        """The device twins of the {val,test} post-processed score-table dicts (None with the flag off)."""
+        bufs = (None, None)
+        if self._device_psds():
+            from .evaluation.psds_device import ScoreBuffer
+            bufs = (ScoreBuffer(), ScoreBuffer())
+        setattr(self, stage + "_scores_device_buffer_student", bufs[0])
+        setattr(self, stage + "_scores_device_buffer_teacher", bufs[1])
 
     def validation_step(self, batch, batch_indx):
         """sed_trainer.py:367-487 with the per-clip host loop of `batched_decode_preds` replaced by the batched device
@@ -834,10 +851,14 @@ class SEDTask4(_Base):
             self.log("val/synth/teacher/loss_strong", bce(strong_t[mask_synth], labels[mask_synth]))
             filenames_synth = [f for f, s in zip(filenames, is_synth) if s]
             win = self.hparams["training"].get("median_window", 7)
-            for preds, buf, post in ((strong_s, self.val_buffer_student_synth, self.val_scores_postprocessed_buffer_student_synth),
-                                     (strong_t, self.val_buffer_teacher_synth, self.val_scores_postprocessed_buffer_teacher_synth)):
+            for preds, buf, post, dev_buf in (
+                    (strong_s, self.val_buffer_student_synth, self.val_scores_postprocessed_buffer_student_synth,
+                     self.val_scores_device_buffer_student),
+                    (strong_t, self.val_buffer_teacher_synth, self.val_scores_postprocessed_buffer_teacher_synth,
+                     self.val_scores_device_buffer_teacher)):
                 _, scores_post, decoded = batched_decode_preds(preds[mask_synth], filenames_synth, self.encoder,
-                                                               median_filter=win, thresholds=list(buf.keys()))
+                                                               median_filter=win, thresholds=list(buf.keys()),
+                                                               device_scores=dev_buf)       # (a ScoreBuffer: no tables are built)
                 post.update(scores_post)
                 for th in buf.keys():
                     buf[th] = pd.concat([buf[th], decoded[th]], ignore_index=True)
@@ -868,10 +889,12 @@ class SEDTask4(_Base):
         data = self.hparams["data"]
         weak_student_f1_macro = self.get_weak_student_f1_seg_macro.compute()
         weak_teacher_f1_macro = self.get_weak_teacher_f1_seg_macro.compute()
-        ground_truth, audio_durations = self._scored_ground_truth(data["synth_val_tsv"], data["synth_val_dur"],
-                                                                  self.val_scores_postprocessed_buffer_student_synth)
+        student_scores = self.val_scores_postprocessed_buffer_student_synth
+        if self.val_scores_device_buffer_student is not None:
+            student_scores = self.val_scores_device_buffer_student
+        ground_truth, audio_durations = self._scored_ground_truth(data["synth_val_tsv"], data["synth_val_dur"], student_scores)
         psds1_student_sed_scores_eval = compute_psds_from_scores(
-            self.val_scores_postprocessed_buffer_student_synth, ground_truth, audio_durations, dtc_threshold=0.7,
+            student_scores, ground_truth, audio_durations, dtc_threshold=0.7,
             gtc_threshold=0.7, cttc_threshold=None, alpha_ct=0, alpha_st=1)
         intersection_f1_macro_student = compute_per_intersection_macro_f1(self.val_buffer_student_synth, data["synth_val_tsv"],
                                                                           data["synth_val_dur"])
@@ -900,6 +923,7 @@ class SEDTask4(_Base):
         self.val_buffer_teacher_synth = {k: pd.DataFrame() for k in ths}
         self.val_scores_postprocessed_buffer_student_synth = {}
         self.val_scores_postprocessed_buffer_teacher_synth = {}
+        self._reset_device_scores("val")
         self.get_weak_student_f1_seg_macro.reset()
         self.get_weak_teacher_f1_seg_macro.reset()
         return obj_metric
@@ -928,6 +952,8 @@ class SEDTask4(_Base):
             self.test_scores_raw_buffer_teacher = {}
             self.test_scores_postprocessed_buffer_student = {}
             self.test_scores_postprocessed_buffer_teacher = {}
+        if not hasattr(self, "test_scores_device_buffer_student"):
+            self._reset_device_scores("test")
 
     def test_step(self, batch, batch_indx):
         """sed_trainer.py:608-683: student and teacher posteriors of one batch, median-filtered and decoded at the
@@ -948,13 +974,14 @@ class SEDTask4(_Base):
             self.log("test/student/loss_strong", bce(strong_s, labels))
             self.log("test/teacher/loss_strong", bce(strong_t, labels))
         win = self.hparams["training"].get("median_window", 7)
-        for preds, psds_buf, raw, post, who in (
+        for preds, psds_buf, raw, post, who, dev_buf in (
                 (strong_s, self.test_psds_buffer_student, self.test_scores_raw_buffer_student,
-                 self.test_scores_postprocessed_buffer_student, "student"),
+                 self.test_scores_postprocessed_buffer_student, "student", self.test_scores_device_buffer_student),
                 (strong_t, self.test_psds_buffer_teacher, self.test_scores_raw_buffer_teacher,
-                 self.test_scores_postprocessed_buffer_teacher, "teacher")):
+                 self.test_scores_postprocessed_buffer_teacher, "teacher", self.test_scores_device_buffer_teacher)):
             scores_raw, scores_post, decoded = batched_decode_preds(preds, filenames, self.encoder, median_filter=win,
-                                                                    thresholds=list(psds_buf.keys()) + [0.5])
+                                                                    thresholds=list(psds_buf.keys()) + [0.5],
+                                                                    device_scores=dev_buf)  # (a ScoreBuffer: no tables are built)
             raw.update(scores_raw)
             post.update(scores_post)
             for th in psds_buf.keys():
@@ -986,11 +1013,13 @@ class SEDTask4(_Base):
         else:
             data = self.hparams["data"]
             results = {}
-            ground_truth, audio_durations = self._scored_ground_truth(data["test_tsv"], data["test_dur"],
-                                                                      self.test_scores_postprocessed_buffer_student)
+            post_s, post_t = self.test_scores_postprocessed_buffer_student, self.test_scores_postprocessed_buffer_teacher
+            if self.test_scores_device_buffer_student is not None:
+                post_s, post_t = self.test_scores_device_buffer_student, self.test_scores_device_buffer_teacher
+            ground_truth, audio_durations = self._scored_ground_truth(data["test_tsv"], data["test_dur"], post_s)
             for who, buf, buf05, post in (
-                    ("student", self.test_psds_buffer_student, self.decoded_student_05_buffer, self.test_scores_postprocessed_buffer_student),
-                    ("teacher", self.test_psds_buffer_teacher, self.decoded_teacher_05_buffer, self.test_scores_postprocessed_buffer_teacher)):
+                    ("student", self.test_psds_buffer_student, self.decoded_student_05_buffer, post_s),
+                    ("teacher", self.test_psds_buffer_teacher, self.decoded_teacher_05_buffer, post_t)):
                 results[f"test/{who}/psds1_psds_eval"] = compute_psds_from_operating_points(
                     buf, data["test_tsv"], data["test_dur"], dtc_threshold=0.7, gtc_threshold=0.7, alpha_ct=0, alpha_st=1,
                     save_dir=os.path.join(save_dir, who, "scenario1"))

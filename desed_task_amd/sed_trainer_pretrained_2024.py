@@ -208,6 +208,18 @@ class SEDTask4(_SEDTask4):
             self.val_buffer_sed_scores_eval_teacher = {}
             self.get_weak_student_f1_seg_macro = _SEDTask4._MacroF1()
             self.get_weak_teacher_f1_seg_macro = _SEDTask4._MacroF1()
+        if not hasattr(self, "val_scores_device_buffer_student"):
+            self._reset_device_scores("val")
+
+    def _append_device_scores(self, dev_buf, preds, filenames):
+        """`training.device_psds`: the filtered scores of a batch also go to a ScoreBuffer, which only the threshold-free PSDS reads;
+        the other metrics of this recipe read the score tables, so those are still built."""
+        from .postprocess import _btc, _filter_batch
+        if dev_buf is None:
+            return
+        scores = _filter_batch(_btc(preds), self.median_filter)
+        dev_buf.append(scores, [Path(f).stem for f in filenames], timestamps=self.encoder._frame_to_time(np.arange(scores.shape[1] + 1)),
+                       event_classes=self.encoder.labels)
 
     def _eval_forward(self, audio, embeddings, classes_mask=None):
         """Eval-mode forward of student and teacher on the same features (the reference's two `detect` calls)."""
@@ -243,10 +255,12 @@ class SEDTask4(_SEDTask4):
             self.log("val/synth/student/loss_strong", bce(strong_s[mask_strong], labels[mask_strong]))
             self.log("val/synth/teacher/loss_strong", bce(strong_t[mask_strong], labels[mask_strong]))
             filenames_strong = [f for f, m in zip(filenames, is_strong) if m]
-            for preds, buf in ((strong_s, self.val_buffer_sed_scores_eval_student), (strong_t, self.val_buffer_sed_scores_eval_teacher)):
+            for preds, buf, dev_buf in ((strong_s, self.val_buffer_sed_scores_eval_student, self.val_scores_device_buffer_student),
+                                        (strong_t, self.val_buffer_sed_scores_eval_teacher, self.val_scores_device_buffer_teacher)):
                 _, scores_post, _ = batched_decode_preds(preds[mask_strong], filenames_strong, self.encoder,
                                                          median_filter=self.median_filter, thresholds=[])
                 buf.update(scores_post)
+                self._append_device_scores(dev_buf, preds[mask_strong], filenames_strong)
         return
 
     @staticmethod
@@ -296,6 +310,14 @@ class SEDTask4(_SEDTask4):
         keys = ["onset", "offset"] + desed
         return {k: buffer[k][keys] for k in ground_truth}, ground_truth, durations
 
+    def _psds_from_scores(self, tables, dev_buf, ground_truth, durations, **kw):
+        """compute_psds_from_scores on the DESED score tables, or with `training.device_psds` on the ScoreBuffer with the DESED
+        columns selected (the tables are then only what `save_dir` writes)."""
+        from .evaluation.evaluation_measures import compute_psds_from_scores
+        if dev_buf is None:
+            return compute_psds_from_scores(tables, ground_truth, durations, **kw)
+        return compute_psds_from_scores(dev_buf, ground_truth, durations, classes=self.class_lists()[0], tables=tables, **kw)
+
     def _maestro_gt(self, tsv, eval_classes):
         import pandas as pd
         from .evaluation.psds_scores import read_ground_truth_events
@@ -312,7 +334,6 @@ class SEDTask4(_SEDTask4):
 
     def validation_epoch_end(self, outputs=None):
         """:575-821 -- same metrics, objective selection, logged keys and buffer resets."""
-        from .evaluation.evaluation_measures import compute_psds_from_scores
         from .evaluation.maestro import merge_overlapping_events
         self._val_state()
         data = self.hparams["data"]
@@ -320,10 +341,11 @@ class SEDTask4(_SEDTask4):
         weak_student_f1_macro = self.get_weak_student_f1_seg_macro.compute()
         weak_teacher_f1_macro = self.get_weak_teacher_f1_seg_macro.compute()
         res = {}
-        for who, buf in (("student", self.val_buffer_sed_scores_eval_student), ("teacher", self.val_buffer_sed_scores_eval_teacher)):
+        for who, buf, dev_buf in (("student", self.val_buffer_sed_scores_eval_student, self.val_scores_device_buffer_student),
+                                  ("teacher", self.val_buffer_sed_scores_eval_teacher, self.val_scores_device_buffer_teacher)):
             scores, gt, dur = self._desed_scores(buf, data["synth_val_tsv"], data["synth_val_dur"])
-            res[who, "psds1"] = compute_psds_from_scores(scores, gt, dur, dtc_threshold=0.7, gtc_threshold=0.7, cttc_threshold=None,
-                                                         alpha_ct=0, alpha_st=1)
+            res[who, "psds1"] = self._psds_from_scores(scores, dev_buf, gt, dur, dtc_threshold=0.7, gtc_threshold=0.7,
+                                                       cttc_threshold=None, alpha_ct=0, alpha_st=1)
             res[who, "inter"], res[who, "collar"] = self._desed_f1_at_05(scores, gt, dur)
         maestro_gt = {k: v for k, v in self._maestro_gt(data["real_maestro_train_tsv"], maestro_eval).items()
                       if k in self.val_buffer_sed_scores_eval_student}
@@ -359,6 +381,7 @@ class SEDTask4(_SEDTask4):
             self.log(f"val/{who}/segment_mpauc/sed_scores_eval", res[who, "mpauc"])
         self.val_buffer_sed_scores_eval_student = {}
         self.val_buffer_sed_scores_eval_teacher = {}
+        self._reset_device_scores("val")
         self.get_weak_student_f1_seg_macro.reset()
         self.get_weak_teacher_f1_seg_macro.reset()
         return obj_metric
@@ -377,6 +400,8 @@ class SEDTask4(_SEDTask4):
             self.test_buffer_sed_scores_eval_unprocessed_teacher = {}
             self.test_buffer_detections_thres05_student = pd.DataFrame()
             self.test_buffer_detections_thres05_teacher = pd.DataFrame()
+        if not hasattr(self, "test_scores_device_buffer_student"):
+            self._reset_device_scores("test")
 
     def test_step(self, batch, batch_indx):
         """:828-922: posteriors without classes_mask, class-wise filtered and decoded at the n_test_thresholds + 0.5 on the
@@ -396,6 +421,7 @@ class SEDTask4(_SEDTask4):
                                                       thresholds=list(psds_buf.keys()) + [0.5])
             getattr(self, f"test_buffer_sed_scores_eval_unprocessed_{who}").update(raw)
             getattr(self, f"test_buffer_sed_scores_eval_{who}").update(post)
+            self._append_device_scores(getattr(self, f"test_scores_device_buffer_{who}"), preds, filenames)
             for th in psds_buf.keys():
                 psds_buf[th] = pd.concat([psds_buf[th], decoded[th]], ignore_index=True)
             name = f"test_buffer_detections_thres05_{who}"
@@ -406,7 +432,7 @@ class SEDTask4(_SEDTask4):
         Otherwise the 22 `test/...` keys; the MAESTRO segment score tables are written under {student,teacher}/maestro/postprocessed."""
         import pandas as pd
         from .evaluation.evaluation_measures import (compute_per_intersection_macro_f1, compute_psds_from_operating_points,
-                                                     compute_psds_from_scores, log_sedeval_metrics)
+                                                     log_sedeval_metrics)
         from .evaluation.maestro import merge_maestro_ground_truth, segment_scores_and_overlap_add
         from .evaluation.psds_scores import read_audio_durations
         from .postprocess import write_sed_scores
@@ -443,10 +469,11 @@ class SEDTask4(_SEDTask4):
                     {"0.5": buf05}, data["test_tsv"], data["test_dur"])
                 results[f"test/{who}/collar_f1_macro_thres05/sed_eval"] = log_sedeval_metrics(buf05, data["test_tsv"], d)[0]
                 scores, gt, dur = self._desed_scores(post, data["test_tsv"], data["test_dur"])
-                results[f"test/{who}/psds1/sed_scores_eval"] = compute_psds_from_scores(
-                    scores, gt, dur, cttc_threshold=None, save_dir=os.path.join(d, "scenario1"), **psds1)
-                results[f"test/{who}/psds2/sed_scores_eval"] = compute_psds_from_scores(
-                    scores, gt, dur, save_dir=os.path.join(d, "scenario2"), **psds2)
+                dev_buf = getattr(self, f"test_scores_device_buffer_{who}")
+                results[f"test/{who}/psds1/sed_scores_eval"] = self._psds_from_scores(
+                    scores, dev_buf, gt, dur, cttc_threshold=None, save_dir=os.path.join(d, "scenario1"), **psds1)
+                results[f"test/{who}/psds2/sed_scores_eval"] = self._psds_from_scores(
+                    scores, dev_buf, gt, dur, save_dir=os.path.join(d, "scenario2"), **psds2)
                 (results[f"test/{who}/intersection_f1_macro_thres05/sed_scores_eval"],
                  results[f"test/{who}/collar_f1_macro_thres05/sed_scores_eval"]) = self._desed_f1_at_05(scores, gt, dur)
                 # MAESTRO: device segment means per clip, overlap-add per recording (:1174-1214)

@@ -601,6 +601,32 @@ int sed_attention_relpos_bf16x1(const float* qkv, const float* relb, const float
 #define SED_GATHER_U8 3
 int sed_batch_gather(const void* desc, int n_streams, const int* idx, int n_rows, int chunks_per_row, void* stream);
 
+/* ---- threshold-free PSDS: per-(clip, class) step functions (desed_task_amd/evaluation/psds_device.py) ---------------------------------
+ * NO reference call site: the role is sed_scores_eval.intersection_based.psds, a third-party package the reference only imports
+ * (desed_task/evaluation/evaluation_measures.py:258-304).  The semantics are those of this package's host evaluator,
+ * evaluation/psds_scores.py::_clip_class_steps.  For every clip n and class c (one workgroup each):
+ *     u[0 .. n_u)      the distinct values of scores[n, :, c], ascending (fp32); u[n_u .. T) = +inf
+ *     row 0            threshold below every score; row i + 1: detections = runs of scores > u[i]; row n_u detects nothing
+ *     tp0, fp0, ct0    the counts of row 0 (true positives, false positives, cross triggers on every other class; ct0[c] = 0)
+ *     dtp, dfp, dct    count(row i + 1) - count(row i) for i < n_u, 0 behind
+ * A run of active frames [a, b) is the detection [ts[a], ts[b]) of length dur; with `same` its summed overlap with the class's
+ * ground-truth events it is relevant when same > 0 && same >= dtc * dur.  An event is detected when the summed overlap of the
+ * relevant runs with it is >= gtc * (off - on).  A run that is not relevant is a false positive when its overlap w with
+ * [0, clip_dur] is > 0 and (w >= cttc * dur or cttc_none), and a cross trigger on class k when its summed overlap x with the events
+ * of k is > 0 && >= cttc * dur.  All time arithmetic is float64; overlaps are closed-form interval intersections, so a run that
+ * touches no event yields exactly 0.
+ * scores (N, T, NC) fp32; ts (T + 1) float64 frame boundaries (an input, never recomputed); ev_ptr (N * NC + 1) int32 CSR offsets
+ * into ev_on / ev_off (float64), ordered by (clip, class); clip_dur (N) float64.  count_ct = 0: ct0 and dct are not touched
+ * (may be null).  count_ct needs a cttc (cttc_none = 0).  u, dtp, dfp: (N * NC, T); ct0 (N * NC, NC); dct (N * NC, T, NC); n_u, tp0,
+ * fp0 (N * NC).  No atomics: two launches write identical bytes.  T > SED_PSDS_MAX_T or NC > SED_PSDS_MAX_NC: SED_ERR_UNSUPPORTED
+ * (there is no host fallback).  Scores must not be NaN (the host layer refuses them). */
+#define SED_PSDS_MAX_T 256
+#define SED_PSDS_MAX_NC 32
+int sed_psds_steps(const float* scores, const double* ts, const int* ev_ptr, const double* ev_on, const double* ev_off,
+                   const double* clip_dur, int N, int T, int NC, double dtc, double gtc, double cttc, int cttc_none,
+                   int count_ct, int* n_u, float* u, int* tp0, int* fp0, int* ct0, int* dtp, int* dfp, int* dct,
+                   void* stream);
+
 /* Tuning overrides for tests / sweep tools / A-B runs (no reference counterpart).  value 0 restores the built-in choice.  Keys:
  *   0  persistent-grid cap of the wide GLU kernels            1  128-channel GLU backward: 1 = 32x32x16 split tiling, 3 = exact f32
  *   2  channels per weight chunk of the split-bf16 conv       3  pixels per workgroup of the split-bf16 conv
