@@ -79,7 +79,16 @@ def compute_sed_eval_metrics(predictions, groundtruth):
 
 def log_sedeval_metrics(predictions, ground_truth, save_dir=None):
     """(event macro-F1, event micro-F1, segment macro-F1, segment micro-F1); `ground_truth` is a TSV path
-    (recipes/dcase2023_task4_baseline/local/utils.py:97-127)."""
+    (recipes/dcase2023_task4_baseline/local/utils.py:97-127).
+
+    `predictions` may also be a f1_device.DecodedScores (a ScoreBuffer seen at one threshold): the per-clip counting then runs in
+    the `sed_f1_counts` kernel (f1_device.sedeval_f1).  With `save_dir` the report texts need the substitutions and accuracies,
+    which the kernel does not count: the host path then runs on the frame `to_dataframe()` builds, so the files are identical."""
+    from .f1_device import DecodedScores, sedeval_f1
+    if isinstance(predictions, DecodedScores):
+        if save_dir is None:
+            return sedeval_f1(predictions, ground_truth)
+        predictions = predictions.to_dataframe()
     if predictions.empty:
         return 0.0, 0.0, 0.0, 0.0
     gt = pd.read_csv(ground_truth, sep="\t")
@@ -102,7 +111,14 @@ def _read(table):
 def compute_per_intersection_macro_f1(prediction_dfs, ground_truth_file, durations_file, dtc_threshold=0.5,
                                       gtc_threshold=0.5, cttc_threshold=0.3):
     """Mean over the thresholds of `prediction_dfs` of the intersection-based macro F1 (evaluation_measures.py:153-195).
-    The two tables may be TSV paths (as in the reference) or DataFrames."""
+    The two tables may be TSV paths (as in the reference) or DataFrames.
+
+    The values of `prediction_dfs` may also be f1_device.DecodedScores of one ScoreBuffer: all thresholds are then counted by one
+    launch of the `sed_f1_counts` kernel (f1_device.intersection_macro_f1)."""
+    from .f1_device import DecodedScores, intersection_macro_f1
+    if any(isinstance(v, DecodedScores) for v in prediction_dfs.values()):
+        return intersection_macro_f1(prediction_dfs, ground_truth_file, durations_file, dtc_threshold=dtc_threshold,
+                                     gtc_threshold=gtc_threshold, cttc_threshold=cttc_threshold)
     psds = PSDSEval(ground_truth=_read(ground_truth_file), metadata=_read(durations_file), dtc_threshold=dtc_threshold,
                     gtc_threshold=gtc_threshold, cttc_threshold=cttc_threshold)
     psds_macro_f1 = []

@@ -282,13 +282,18 @@ class PSDSEval:
         any true positive yields NaN and is skipped by the nan-mean (all classes without TP -> NaN, which the reference
         maps to 0 at evaluation_measures.py:192-193)."""
         counts, tpr, _, _ = self._evaluate_detections(self._init_det_table(detections))
-        tp = np.diag(counts)[:-1]
+        return self._macro_f_tail(np.diag(counts)[:-1], counts[:-1, -1], tpr, self.class_names[:-1], beta)
+
+    @classmethod
+    def _macro_f_tail(cls, tp, fp, tpr, class_names, beta=1.0):
+        """The F scores from the per-class true positives, false positives (WORLD column) and true-positive ratios: shared with
+        evaluation/f1_device.py, which counts tp and fp on the device."""
         with np.errstate(divide="ignore", invalid="ignore"):
             n_gt = tp / tpr
-        f = self.compute_f_score(tp, counts[:-1, -1], n_gt - tp, beta)
+        f = cls.compute_f_score(tp, fp, n_gt - tp, beta)
         with np.errstate(invalid="ignore"):
             import warnings
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore", RuntimeWarning)
                 f_avg = float(np.nanmean(f))
-        return f_avg, {c: float(v) for c, v in zip(self.class_names[:-1], f)}
+        return f_avg, {c: float(v) for c, v in zip(class_names, f)}

@@ -145,6 +145,26 @@ def _event_table_on(table, device):
     return table["dev"][key]
 
 
+def _score_columns(buffer, ids, classes):
+    """-> (class names, (len(ids), T, NC) contiguous device scores) of the clips `ids`: all columns of the buffer, or the columns
+    `classes` names, in that order.  NaN scores are refused."""
+    if buffer.event_classes is None or buffer.timestamps is None:
+        raise ValueError("the ScoreBuffer has no timestamps / event classes")
+    scores = buffer.rows(ids)
+    if classes is None:
+        classes = list(buffer.event_classes)
+    else:
+        classes = list(classes)
+        unknown = [c for c in classes if c not in buffer.event_classes]
+        if unknown:
+            raise ValueError("classes without a score column: %s" % unknown[:3])
+        cols = torch.tensor([buffer.event_classes.index(c) for c in classes], dtype=torch.long, device=scores.device)
+        scores = scores.index_select(2, cols).contiguous()
+    if bool(torch.isnan(scores).any()):
+        raise ValueError("the scores hold NaN")
+    return classes, scores
+
+
 def psds_steps(scores, ts, ev_ptr, ev_on, ev_off, clip_dur, dtc, gtc, cttc, count_ct, out=None):
     """The kernel: scores (N, T, NC) fp32, ts (T + 1) / ev_on / ev_off / clip_dur float64, ev_ptr (N * NC + 1) int32, all on the
     device.  cttc None: no cross-trigger threshold.  -> dict of device tensors n_u, tp0, fp0 (N, NC) int32, u (N, NC, T) fp32, dtp,
@@ -217,20 +237,7 @@ def psds_from_score_buffer(buffer, ground_truth, audio_durations, dtc_threshold=
         raise ValueError("scores / durations missing for %d clips, e.g. %s" % (len(missing), missing[:3]))
     if not ids:
         raise ValueError("no clips to evaluate")
-    if buffer.event_classes is None or buffer.timestamps is None:
-        raise ValueError("the ScoreBuffer has no timestamps / event classes")
-    scores = buffer.rows(ids)
-    if classes is None:
-        classes = list(buffer.event_classes)
-    else:
-        classes = list(classes)
-        unknown = [c for c in classes if c not in buffer.event_classes]
-        if unknown:
-            raise ValueError("classes without a score column: %s" % unknown[:3])
-        cols = torch.tensor([buffer.event_classes.index(c) for c in classes], dtype=torch.long, device=scores.device)
-        scores = scores.index_select(2, cols).contiguous()
-    if bool(torch.isnan(scores).any()):
-        raise ValueError("the scores hold NaN")
+    classes, scores = _score_columns(buffer, ids, classes)
     dev = scores.device
     nsec = PSDSEval.secs_in_uot[unit_of_time]
     use_ct = cttc_threshold is not None and alpha_ct > 0

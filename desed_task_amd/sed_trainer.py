@@ -809,6 +809,17 @@ class SEDTask4(_Base):
         only writes tables and keeps the host path."""
         return bool(self.hparams["training"].get("device_psds", False)) and not self.evaluation
 
+    def _device_f1(self):
+        """`training.device_f1: True` (default off): the validation hooks decode nothing on the host; the collar and intersection F1
+        are counted from the ScoreBuffers by the `sed_f1_counts` kernel (evaluation/f1_device.py).  It reads the buffers that
+        `training.device_psds` keeps, so it needs that flag.  `evaluation=True` keeps the host path."""
+        training = self.hparams["training"]
+        if not training.get("device_f1", False):
+            return False
+        if not training.get("device_psds", False):
+            raise ValueError("training.device_f1 needs training.device_psds: both read the same ScoreBuffer per model")
+        return not self.evaluation
+
     def _reset_device_scores(self, stage):
         """The device twins of the {val,test} post-processed score-table dicts (None with the flag off)."""
         bufs = (None, None)
@@ -826,6 +837,7 @@ class SEDTask4(_Base):
         import pandas as pd
         from .postprocess import batched_decode_preds
         self._val_state()
+        device_f1 = self._device_f1()
         audio, labels, padded_indxs, filenames = batch[0], batch[1], batch[2], batch[3]
         bce = torch.nn.functional.binary_cross_entropy
         emb = self._eval_embeddings(batch)
@@ -856,11 +868,12 @@ class SEDTask4(_Base):
                      self.val_scores_device_buffer_student),
                     (strong_t, self.val_buffer_teacher_synth, self.val_scores_postprocessed_buffer_teacher_synth,
                      self.val_scores_device_buffer_teacher)):
+                # device_f1: no thresholds -- no region launch, no event copy, no frames; the epoch end reads the ScoreBuffer
                 _, scores_post, decoded = batched_decode_preds(preds[mask_synth], filenames_synth, self.encoder,
-                                                               median_filter=win, thresholds=list(buf.keys()),
+                                                               median_filter=win, thresholds=[] if device_f1 else list(buf.keys()),
                                                                device_scores=dev_buf)       # (a ScoreBuffer: no tables are built)
                 post.update(scores_post)
-                for th in buf.keys():
+                for th in decoded.keys():
                     buf[th] = pd.concat([buf[th], decoded[th]], ignore_index=True)
         return
 
@@ -883,6 +896,7 @@ class SEDTask4(_Base):
         from .evaluation.evaluation_measures import (compute_per_intersection_macro_f1, compute_psds_from_scores,
                                                      log_sedeval_metrics)
         self._val_state()
+        device_f1 = self._device_f1()
         obj_type = self.hparams["training"].get("obj_metric_synth_type")
         if obj_type not in (None, "psds", "event", "intersection"):
             raise NotImplementedError(f"obj_metric_synth_type: {obj_type} not implemented.")
@@ -896,12 +910,17 @@ class SEDTask4(_Base):
         psds1_student_sed_scores_eval = compute_psds_from_scores(
             student_scores, ground_truth, audio_durations, dtc_threshold=0.7,
             gtc_threshold=0.7, cttc_threshold=None, alpha_ct=0, alpha_st=1)
-        intersection_f1_macro_student = compute_per_intersection_macro_f1(self.val_buffer_student_synth, data["synth_val_tsv"],
+        decoded_student, decoded_teacher = self.val_buffer_student_synth, self.val_buffer_teacher_synth
+        if device_f1:                    # the frames were never built: the ScoreBuffers seen at the same thresholds
+            from .evaluation.f1_device import DecodedScores
+            decoded_student = {th: DecodedScores(self.val_scores_device_buffer_student, th) for th in decoded_student}
+            decoded_teacher = {th: DecodedScores(self.val_scores_device_buffer_teacher, th) for th in decoded_teacher}
+        intersection_f1_macro_student = compute_per_intersection_macro_f1(decoded_student, data["synth_val_tsv"],
                                                                           data["synth_val_dur"])
-        synth_student_event_macro = log_sedeval_metrics(self.val_buffer_student_synth[0.5], data["synth_val_tsv"])[0]
-        intersection_f1_macro_teacher = compute_per_intersection_macro_f1(self.val_buffer_teacher_synth, data["synth_val_tsv"],
+        synth_student_event_macro = log_sedeval_metrics(decoded_student[0.5], data["synth_val_tsv"])[0]
+        intersection_f1_macro_teacher = compute_per_intersection_macro_f1(decoded_teacher, data["synth_val_tsv"],
                                                                           data["synth_val_dur"])
-        synth_teacher_event_macro = log_sedeval_metrics(self.val_buffer_teacher_synth[0.5], data["synth_val_tsv"])[0]
+        synth_teacher_event_macro = log_sedeval_metrics(decoded_teacher[0.5], data["synth_val_tsv"])[0]
         if obj_type in (None, "psds"):
             synth_metric = psds1_student_sed_scores_eval
         elif obj_type == "event":

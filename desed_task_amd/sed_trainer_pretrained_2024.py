@@ -286,12 +286,21 @@ class SEDTask4(_SEDTask4):
         meta = pd.DataFrame([(k + ".wav", durations[k]) for k in ground_truth], columns=["filename", "duration"])
         return gt, meta
 
-    def _desed_f1_at_05(self, scores, ground_truth, durations):
+    def _desed_f1_at_05(self, scores, ground_truth, durations, dev_buf=None):
         """sed_scores_eval's intersection_based.fscore (dtc = gtc = 0.5) and collar_based.fscore (200 ms collar, 20 % offset
-        rate) macro averages at threshold 0.5 (:617-636), on psds.PSDSEval and sed_eval_metrics.EventBasedMetrics."""
+        rate) macro averages at threshold 0.5 (:617-636), on psds.PSDSEval and sed_eval_metrics.EventBasedMetrics.  With
+        `training.device_f1` the detections are not decoded: both scores are counted from `dev_buf`, the DESED columns of the
+        scored clips, by the `sed_f1_counts` kernel (evaluation/f1_device.py)."""
         from .evaluation.evaluation_measures import compute_per_intersection_macro_f1, event_based_evaluation_df
-        det = self._detections(scores, 0.5)
         gt, meta = self._event_table(ground_truth, durations)
+        if dev_buf is not None and self._device_f1():
+            from .evaluation.f1_device import DecodedScores, sedeval_f1
+            det = DecodedScores(dev_buf, 0.5, classes=self.class_lists()[0], ids=list(scores))
+            inter = compute_per_intersection_macro_f1({"0.5": det}, gt, meta, dtc_threshold=0.5, gtc_threshold=0.5)
+            if det.empty:
+                return float(inter), 0.0
+            return float(inter), float(sedeval_f1(det, gt, t_collar=0.2, percentage_of_length=0.2)[0])
+        det = self._detections(scores, 0.5)
         inter = compute_per_intersection_macro_f1({"0.5": det}, gt, meta, dtc_threshold=0.5, gtc_threshold=0.5)
         if det.empty:
             return float(inter), 0.0
@@ -346,7 +355,7 @@ class SEDTask4(_SEDTask4):
             scores, gt, dur = self._desed_scores(buf, data["synth_val_tsv"], data["synth_val_dur"])
             res[who, "psds1"] = self._psds_from_scores(scores, dev_buf, gt, dur, dtc_threshold=0.7, gtc_threshold=0.7,
                                                        cttc_threshold=None, alpha_ct=0, alpha_st=1)
-            res[who, "inter"], res[who, "collar"] = self._desed_f1_at_05(scores, gt, dur)
+            res[who, "inter"], res[who, "collar"] = self._desed_f1_at_05(scores, gt, dur, dev_buf)
         maestro_gt = {k: v for k, v in self._maestro_gt(data["real_maestro_train_tsv"], maestro_eval).items()
                       if k in self.val_buffer_sed_scores_eval_student}
         maestro_gt = merge_overlapping_events(maestro_gt)
@@ -475,7 +484,7 @@ class SEDTask4(_SEDTask4):
                 results[f"test/{who}/psds2/sed_scores_eval"] = self._psds_from_scores(
                     scores, dev_buf, gt, dur, save_dir=os.path.join(d, "scenario2"), **psds2)
                 (results[f"test/{who}/intersection_f1_macro_thres05/sed_scores_eval"],
-                 results[f"test/{who}/collar_f1_macro_thres05/sed_scores_eval"]) = self._desed_f1_at_05(scores, gt, dur)
+                 results[f"test/{who}/collar_f1_macro_thres05/sed_scores_eval"]) = self._desed_f1_at_05(scores, gt, dur, dev_buf)
                 # MAESTRO: device segment means per clip, overlap-add per recording (:1174-1214)
                 seg = segment_scores_and_overlap_add({k: post[k] for k in maestro_clip_ids}, maestro_dur, maestro_real,
                                                      segment_length=1.0, device=self._eval_device())

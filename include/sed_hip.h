@@ -627,6 +627,43 @@ int sed_psds_steps(const float* scores, const double* ts, const int* ev_ptr, con
                    int count_ct, int* n_u, float* u, int* tp0, int* fp0, int* ct0, int* dtp, int* dfp, int* dct,
                    void* stream);
 
+/* ---- collar, segment and intersection F1 counts per (threshold, clip, class) (desed_task_amd/evaluation/f1_device.py) ---------------
+ * NO reference call site: the roles are sed_eval's event-based / segment-based metrics and psds_eval's F score, third-party packages
+ * the reference only imports (desed_task/evaluation/evaluation_measures.py:50-195).  The semantics are those of this package's host
+ * evaluators: sed_eval_metrics.EventBasedMetrics / SegmentBasedMetrics and psds.PSDSEval._evaluate_detections.
+ * A detection of (k, n, c) is a run [a, b) of scores[n, :, c] > thr[k] (strict, fp32, as sed_threshold_events) and is the event
+ * [ts[a], ts[b]); there are at most (T + 1) / 2.  counts[k, n, c, 0 .. 8), with (on_r, off_r) a ground-truth event of (n, c) and
+ * (on_s, off_s) a run:
+ *     0 n_sys      the number of runs
+ *     1 collar_tp  size of a MAXIMUM bipartite matching of the events and the runs under
+ *                  fabs(on_r - on_s) <= t_collar && fabs(off_r - off_s) <= max(t_collar, percentage_of_length * (off_r - on_r))
+ *     2 seg_ref    cells of the raster [floor(on / time_resolution), ceil(off / time_resolution)) over the events
+ *     3 seg_sys    cells of the same raster over the runs
+ *     4 seg_tp     cells set in both
+ *     5 int_tp     events hit: a run is RELEVANT when it overlaps an event (inter = min(off_s, off_r) - max(on_s, on_r) > 0) and the
+ *                  sum over the events, in table order, of inter / (off_s - on_s) is >= dtc; an event is hit when a relevant run
+ *                  overlaps it and the sum over the relevant runs, in run order, of inter / (off_r - on_r) is >= gtc
+ *     6 int_fp     runs that are not relevant, overlap [0, clip_dur[n]] by w > 0 and have w / (off_s - on_s) >= cttc
+ *     7 0          reserved
+ * All time arithmetic is float64, a ratio per pair and then a sum (psds.py's form; sed_psds_steps compares summed overlaps with
+ * dtc * dur instead).  Cross triggers are not counted.
+ * scores (N, T, NC) fp32; thr (n_thr) fp32; ts (T + 1) float64 frame boundaries (an input, never recomputed); ev_ptr (N * NC + 1)
+ * int32 CSR offsets into ev_on / ev_off (float64), ordered by (clip, class) and inside a class in ground-truth order: the table
+ * sed_psds_steps takes; clip_dur (N) float64; counts (n_thr, N, NC, 8) int32, 16-byte aligned, plain stores, no atomics: two
+ * launches write identical bytes.  T > SED_F1_MAX_T, NC > SED_F1_MAX_NC or n_thr > SED_F1_MAX_THR: SED_ERR_UNSUPPORTED and nothing
+ * is written (there is no host fallback).  Contract the kernel cannot report: at most SED_F1_MAX_EVENTS events per (clip, class)
+ * (further ones are ignored) and every event and ts[T] inside SED_F1_MAX_CELLS raster cells (cells beyond are dropped); the host
+ * layer checks both and raises before any launch.  Scores must not be NaN (the host layer refuses them). */
+#define SED_F1_MAX_T 256
+#define SED_F1_MAX_NC 32
+#define SED_F1_MAX_THR 8
+#define SED_F1_MAX_EVENTS 32
+#define SED_F1_MAX_CELLS 64
+int sed_f1_counts(const float* scores, const float* thr, const double* ts, const int* ev_ptr, const double* ev_on,
+                  const double* ev_off, const double* clip_dur, int N, int T, int NC, int n_thr, double t_collar,
+                  double percentage_of_length, double time_resolution, double dtc, double gtc, double cttc, int* counts,
+                  void* stream);
+
 /* Tuning overrides for tests / sweep tools / A-B runs (no reference counterpart).  value 0 restores the built-in choice.  Keys:
  *   0  persistent-grid cap of the wide GLU kernels            1  128-channel GLU backward: 1 = 32x32x16 split tiling, 3 = exact f32
  *   2  channels per weight chunk of the split-bf16 conv       3  pixels per workgroup of the split-bf16 conv
